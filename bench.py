@@ -18,12 +18,21 @@ phase2_bs128 (config 5, train_image_phase2.py:152-258 incl. the per-sample weigh
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment re-launches itself under
 torch.distributed.run with N ranks (one per GPU, RCCL); under a launcher it just joins the job.
 
-Also on the JSON line:
+A plain run (no --full) sets up, warms up, times --steps steps, writes the last timed step's outputs if --dump-outputs is given,
+and prints the headline line (metric / value / unit / higher_is_better / dtype / ms_per_step / config ...).
+
+--full adds to the JSON line what needs runs or steps of its own:
   roofline      -- the convolution family (MFMA bound): algorithmic FLOP / HIP-event time of every launch of one extra,
                    instrumented step (lbc_profile_* in the C ABI); traffic = HBM bytes per launch from the committed
                    rocprofv3 --pmc passes of this command (profiles/, FETCH_SIZE x 2 + WRITE_SIZE), when available
   roofline_hbm  -- the BatchNorm family (HBM bound): algorithmic bytes / HIP-event time
-  cpu_baseline  -- the oracle's (torch-CPU restatement of the reference) step on the host cores (N = 1 only)
+  also, h2d_inclusive, per_gpu_32 -- short extra runs: exact f32, PCIe-inclusive feed, the 8-GPU run's per-GPU load (--no-alt: off)
+  cpu_baseline  -- the oracle's (torch-CPU restatement of the reference) step on the host cores (N = 1 only; --no-cpu-baseline: off)
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32): the per-sample
+loss the step returns, the student's (and the teacher's) waypoints, the phase-2 weights, the student's float buffers (BatchNorm
+running statistics) and a fixed, seeded sample of 2^20 of its updated parameters (dump_outputs).  The inputs are seeded: the same
+arguments give the same inputs from run to run.
 """
 import argparse
 import json
@@ -251,6 +260,31 @@ def read_traffic():
     return None
 
 
+PARAM_SAMPLE = 1 << 20      # parameter entries --dump-outputs writes (4 MB), drawn once with a fixed seed
+
+
+def dump_outputs(d, tr, loss, weights):
+    """what the last timed step handed its caller, as float32 .npy files under d (see the module docstring)"""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"loss": loss, "student_pred_selected": tr.last_pred[0], "student_pred_all": tr.last_pred[1]}
+    if getattr(tr, "last_teacher", None) is not None:
+        arrays["teacher_pred_selected"], arrays["teacher_pred_all"] = tr.last_teacher
+    if weights:
+        arrays["phase2_weights"] = weights[-1]
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in tr.student.named_parameters()])
+        g = torch.Generator().manual_seed(20240)
+        idx = torch.randperm(flat.numel(), generator=g)[:min(PARAM_SAMPLE, flat.numel())].sort().values
+        arrays["student_params_sample"] = flat[idx.to(flat.device)]
+        bufs = [b.detach().reshape(-1).float() for b in tr.student.buffers() if b.dtype.is_floating_point]
+        if bufs:
+            arrays["student_buffers"] = torch.cat(bufs)
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -275,14 +309,22 @@ def main():
                                                        "(double-buffered): the PCIe-inclusive rate.  Default: the dataset is resident in HBM")
     ap.add_argument("--resident", action="store_true", help="re-feed ONE device-resident batch every step")
     ap.add_argument("--init-steps", type=int, default=40, help="below-horizon warm start (stands in for the phase-0 checkpoint)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the short extra runs of the default line: exact f32 ('also'), PCIe-inclusive "
+    ap.add_argument("--full", action="store_true", help="also measure what needs steps or runs of its own: the instrumented step (roofline, "
+                                                        "roofline_hbm), the short extra runs (--no-alt) and the CPU baseline (--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the short extra runs: exact f32 ('also'), PCIe-inclusive "
                                                           "('h2d_inclusive') and the 32-image per-GPU load of the 8-GPU run ('per_gpu_32')")
-    ap.add_argument("--breakdown", default=None, help="write the per-kernel-class profile of the instrumented step here (json)")
+    ap.add_argument("--breakdown", default=None, help="--full: write the per-kernel-class profile of the instrumented step here (json)")
     ap.add_argument("--serial", action="store_true",
                     help="profiling runs: the teacher forward stays on the main stream (with LBC_NO_SIDE_STREAM=1 every kernel then runs alone, "
                          "so that rocprofv3 per-kernel durations are not inflated by co-running kernels)")
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown reports the instrumented step, which only --full runs")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = WORKLOADS[args.workload]
     kind = wl["kind"]
     global_batch = args.global_batch or wl["batch"]
@@ -315,7 +357,7 @@ def main():
     assert per_gpu * world == global_batch, "global batch must divide by the number of GPUs"
     host_pool = FramePool(per_gpu if args.resident else args.pool_frames, per_gpu, device, 1000 + rank, need_rgb=kind != "birdview", slots=True)
     # the default feed: everything the timed region reads lives in HBM (the pinned host copy only serves --h2d and the short
-    # PCIe-inclusive run the default line reports next to the headline number)
+    # PCIe-inclusive run the --full line reports next to the headline number)
     dev_pool = None if (args.h2d or args.resident) else DevicePool(host_pool)
     cur = {"pool": host_pool if dev_pool is None else dev_pool, "pg": per_gpu}
     # Warm start below the horizon: the phase-1 unprojection has a 1/y pole at the horizon and the reference always
@@ -395,7 +437,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return tr, float(t.item()), float(loss.mean().item())
+        return tr, float(t.item()), float(loss.mean().item()), (loss, weights)
 
     def instrumented_step(tr, dt_name):
         """one extra step with HIP events around every launch (every rank runs it -- it contains the all-reduce -- rank 0 reports)"""
@@ -453,10 +495,13 @@ def main():
                "non_conv_kernel_ms_per_step": round(total_ms - ms, 3)}
         return roof, hbm, br
 
-    tr, dt, loss_mean = timed_run(dtype, args.steps, args.warmup)
+    tr, dt, loss_mean, (last_loss, last_weights) = timed_run(dtype, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr, last_loss, last_weights)
     # the ranks the gradient buckets really travel between: a one from every rank summed on the buckets' own communicator and stream
     comm_ranks = tr.reducer.participants() if world > 1 else None        # read back from the buckets' communicator, whatever its backend
-    roof, hbm, breakdown = instrumented_step(tr, dtype)
+    if args.full:
+        roof, hbm, breakdown = instrumented_step(tr, dtype)
     if rank == 0 and args.breakdown:
         os.makedirs(os.path.dirname(os.path.abspath(args.breakdown)), exist_ok=True)
         with open(args.breakdown, "w") as f:
@@ -483,15 +528,22 @@ def main():
                           "global_batch": global_batch, "parallelism": "dp%d" % world,
                           "waypoint_tolerance_vs_f32": WAYPOINT_TOLERANCE[{"f32": "fp32"}.get(dtype, dtype)]},
                "loss": loss_mean, "loss_finite": bool(loss_mean == loss_mean and abs(loss_mean) != float("inf")),
-               "algorithmic_tflops": round(value * wl["gflop"] / 1e3, 2),
-               "roofline": roof, "roofline_hbm": hbm}
+               "algorithmic_tflops": round(value * wl["gflop"] / 1e3, 2)}
+        if args.full:
+            out["roofline"], out["roofline_hbm"] = roof, hbm
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     also = None
     if dtype != "f32" and not args.no_alt:
         # the exact-f32 parity path on the same workload, a short run reported next to the headline number
         del tr
         torch.cuda.empty_cache()
         asteps = max(3, min(20, args.steps // 2))
-        atr, adt, aloss = timed_run("f32", asteps, 2)
+        atr, adt, aloss, _ = timed_run("f32", asteps, 2)
         aroof, ahbm, _ = instrumented_step(atr, "f32")
         also = {"dtype": "f32", "value": round(global_batch * asteps / adt, 2), "ms_per_step": round(1e3 * adt / asteps, 3),
                 "steps": asteps, "note": "exact-f32 MFMA path (the one held to the 1e-3 waypoint parity bar)", "roofline": aroof, "roofline_hbm": ahbm}
@@ -502,7 +554,7 @@ def main():
         torch.cuda.empty_cache()
         hsteps = max(5, min(20, args.steps // 2))
         host_pool.pos = 0
-        htr, hdt, _ = timed_run(dtype, hsteps, 5, pool=host_pool)
+        htr, hdt, _, _ = timed_run(dtype, hsteps, 5, pool=host_pool)
         h2d_incl = {"ms_per_step": round(1e3 * hdt / hsteps, 3), "value": round(global_batch * hsteps / hdt, 2), "steps": hsteps,
                     "h2d_mb_per_step": round(host_pool.bytes_per_step / 1e6, 1),
                     "note": "the same step with the uint8 frames uploaded from pinned host memory inside the timed region (double-buffered): the PCIe-inclusive rate"}
@@ -510,7 +562,7 @@ def main():
         # (b) the metric's 8-GPU operating point is 32 images per GPU: that load on this one GPU (no communication), with its own roofline
         if kind == "phase1" and global_batch == 256:
             torch.cuda.empty_cache()
-            str_, sdt, _ = timed_run(dtype, 30, 10, pool=dev_pool, pg=32)
+            str_, sdt, _, _ = timed_run(dtype, 30, 10, pool=dev_pool, pg=32)
             sroof, shbm, _ = instrumented_step(str_, dtype)
             small = {"per_gpu_batch": 32, "ms_per_step": round(1e3 * sdt / 30, 3), "value_one_gpu": round(32 * 30 / sdt, 2), "steps": 30,
                      "no_comm_projection_8gpu": round(8 * 32 * 30 / sdt, 1),

@@ -76,23 +76,44 @@ def test_weights_are_channels_last_and_survive_load_and_to():
     assert list(out.keys()) == list(sd.keys())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/bird_view"), reason="reference checkout only exists in the build container")
+def _recorded_reference_module(layout):
+    """a module whose state_dict holds exactly the (key, shape, dtype) entries the REAL reference class had when oracle/make_golden.py
+    recorded tests/golden/state_dict_layout.json: a strict load_state_dict into it checks what the reference class's strict load checks
+    (the key set and every shape), and what it saves has the reference checkpoint's keys, shapes and dtypes"""
+    root = torch.nn.Module()
+    for key, shape, dt in layout:
+        *path, leaf = key.split(".")
+        m = root
+        for p in path:
+            if p not in m._modules:
+                m.add_module(p, torch.nn.Module())
+            m = m._modules[p]
+        m.register_buffer(leaf, torch.zeros(shape, dtype=getattr(torch, dt.split(".", 1)[1])))
+    return root
+
+
 def test_checkpoint_round_trip_with_reference_classes(tmp_path):
-    """our .th -> reference class (strict) and reference .th -> ours, through the logic of benchmark_agent.py:27-38"""
+    """our .th -> reference class (strict) and reference .th -> ours, through the logic of benchmark_agent.py:27-38; the reference
+    class is stood in for by its recorded state_dict layout (tests/golden), so the check runs wherever the suite runs"""
     from learningbycheating_amd.bird_view.models import ImagePolicyModelSS, BirdViewPolicyModelSS
-    from oracle import ref_shim, lbc_oracle as O
+    from oracle import lbc_oracle as O
+    lay = json.load(open(os.path.join(GOLD, "state_dict_layout.json")))
     for kind, backbone, ours in (("image", "resnet34", ImagePolicyModelSS), ("birdview", "resnet18", BirdViewPolicyModelSS)):
         mine = ours(backbone)
         mine.load_state_dict(O.make_state_dict(kind, backbone, 17))
         path = tmp_path / ("model-%s.th" % kind)
         torch.save(mine.state_dict(), str(path))
         config = {"model_args": {"model": "image_ss" if kind == "image" else "birdview_dian", "backbone": backbone, "imagenet_pretrained": False}}
-        ref = ref_shim.build(kind, **{k: v for k, v in config["model_args"].items() if k != "backbone"}, backbone=backbone) if kind == "image" \
-            else ref_shim.build(kind, backbone, **{k: v for k, v in config["model_args"].items() if k != "backbone"})
-        ref.load_state_dict(torch.load(str(path)))          # strict, as benchmark_agent.py:37
+        recorded = lay["%s_%s" % (kind, backbone)]
+        ref = _recorded_reference_module(recorded)
+        saved = torch.load(str(path))
+        assert {k: str(v.dtype) for k, v in saved.items()} == {k: dt for k, _, dt in recorded}
+        ref.load_state_dict(saved)          # strict, as benchmark_agent.py:37
         ref.eval()
         for k, v in ref.state_dict().items():
             assert torch.equal(v, mine.state_dict()[k]), k
+        # a checkpoint written by the reference class: other values, the recorded keys / shapes / dtypes
+        ref.load_state_dict(O.make_state_dict(kind, backbone, 18))
         path2 = tmp_path / ("ref-%s.th" % kind)
         torch.save(ref.state_dict(), str(path2))
         again = ours(**config["model_args"])

@@ -1,5 +1,5 @@
-"""The JSON line bench.py prints is a contract with the driver (metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling /
-dtype / data / config + roofline + cpu_baseline).  CPU-only check of the line the last evidence call of the round committed under profiles/:
+"""The JSON line `bench.py --full` prints is a contract with the driver (metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling /
+dtype / data / config; --full adds roofline + cpu_baseline, which a plain run leaves out).  CPU-only check of the line the last evidence call of the round committed under profiles/:
 the keys the contract names are there, the numbers are consistent with each other, and the blocks round 5 added (PCIe-inclusive rate, the
 32-image per-GPU load of the 8-GPU run) carry what DESIGN.md quotes.  (bench.py itself needs a GPU: the product path has no CPU fallback.)"""
 import glob
@@ -50,3 +50,32 @@ def test_round5_blocks_of_the_default_line():
     assert p["ms_per_step"] < d["ms_per_step"] and 0.0 < p["roofline"]["frac"] < d["roofline"]["frac"]
     also = d["also"]
     assert also["dtype"] == "f32" and also["roofline"]["peak"] < d["roofline"]["peak"]
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: every array the step handed its caller lands as DIR/<name>.npy in float32, and the parameter sample is the same
+    fixed, seeded subset every time (so that two builds can be compared entry for entry)"""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(bench, "PARAM_SAMPLE", 100)
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.BatchNorm2d(8))
+    g = torch.Generator().manual_seed(1)
+    tr = types.SimpleNamespace(student=net, last_pred=(torch.rand((4, 5, 2), generator=g), torch.rand((4, 4, 5, 2), generator=g)),
+                               last_teacher=(torch.rand((4, 5, 2), generator=g), torch.rand((4, 4, 5, 2), generator=g)))
+    loss, weights = torch.rand(4, generator=g, dtype=torch.float64), [torch.rand(4, generator=g)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), tr, loss, weights)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in ("loss", "phase2_weights", "student_buffers", "student_params_sample", "student_pred_all",
+                                                "student_pred_selected", "teacher_pred_all", "teacher_pred_selected"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "student_pred_all.npy"), tr.last_pred[1].numpy())
+    sample = np.load(tmp_path / "a" / "student_params_sample.npy")
+    flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).numpy()
+    assert sample.shape == (100,) and np.isin(sample, flat).all()
