@@ -32,7 +32,7 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      ABI-200 layout (through split_workspace_bytes) up to the library's own sizeof -- fields appended later are optional for older hosts.
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
-#define LBC_HIP_ABI_VERSION 200
+#define LBC_HIP_ABI_VERSION 201
 int lbc_version(void);
 
 typedef struct lbc_conv_desc {
@@ -46,7 +46,11 @@ typedef struct lbc_conv_desc {
                            2: as 1, and the activation tensors (x, y, resid, dy, dx: the `void*` arguments) are bf16 in
                            HBM; weights, bias, statistics and weight gradients stay f32.
                            3: as 2, and `w` of the forward / input-gradient entry points is a bf16 copy of the weights in
-                           the same (depth-contiguous) layout; weight gradients are still produced in f32 */
+                           the same (depth-contiguous) layout; weight gradients are still produced in f32.
+                           4: split bf16 ("bf16x3"): tensors and weights f32 as in 0/1; each MFMA operand v is split into
+                           hi = bf16(v), lo = bf16(v - hi) and the product is hi*hi' + hi*lo' + lo*hi' in f32 (~1e-5
+                           relative instead of 1's ~1e-3).  Needs w_transposed = 1 where 1 does.  No grouped weight
+                           gradient (lbc_conv2d_wgrad_group_supported answers 0); the stem entry points refuse it */
     int w_transposed;   /* lbc_conv2d_dgrad / lbc_deconv3x3s2_fwd only: `w` is the lbc_weight_transpose()d copy (depth-
                            contiguous for these GEMMs).  Required when bf16 = 1. */
     void* split_workspace;          /* optional (NULL = none): device scratch that lets lbc_conv2d_fwd / lbc_conv2d_dgrad launches with */
@@ -122,7 +126,10 @@ typedef struct lbc_net_desc {
     int precision;     /* 0: f32 everywhere (exact-f32 MFMA; the parity path).  1: convolution MFMA operands rounded to
                           bf16 with f32 accumulation; tensors, BatchNorm, softmax, loss, Adam and the stem stay f32.
                           2: as 1, and activations / activation gradients are stored as bf16 in the workspace (all
-                          arithmetic on them stays f32; parameters, gradients, statistics, outputs stay f32) */
+                          arithmetic on them stays f32; parameters, gradients, statistics, outputs stay f32).
+                          3: "bf16x3": every convolution but the stem multiplies split-bf16 operands (lbc_conv_desc.bf16 = 4:
+                          three bf16 MFMAs per fragment pair, f32 accumulation); tensors f32 as in 0, and the input repack, stem,
+                          BatchNorm, head, loss and Adam run their exact-f32 kernels */
 } lbc_net_desc;
 typedef struct lbc_net lbc_net;
 
@@ -281,7 +288,8 @@ int lbc_head_bwd(const lbc_head_desc* d, const float* pred_all, const float* d_a
  * lbc_nchw_to_input / lbc_u8nhwc_to_input: image -> xp[N][H+6][W+6][C] (3-pixel zero border; bf16 when xp_bf16),
  *   optionally ImageNet-normalised (normalize = 1, C = 3).
  * lbc_stem_fwd: xp, w[64][7][7][C] -> y[N][H/2][W/2][64] (+ statistics partial rows, nullable).
- * lbc_stem_wgrad: xp, dy -> dw[64][7][7][C]; workspace lbc_stem_wgrad_workspace() bytes.  bf16: lbc_conv_desc.bf16 modes 0/1/2. */
+ * lbc_stem_wgrad: xp, dy -> dw[64][7][7][C]; workspace lbc_stem_wgrad_workspace() bytes.  bf16: lbc_conv_desc.bf16 modes 0/1/2; other values
+ * (the split mode 4 included: there is no split stem, precision 3 runs the stem with 0) are refused with LBC_EINVAL. */
 int lbc_nchw_to_input(const float* image_nchw, void* xp, int xp_bf16, int N, int C, int H, int W, int normalize, lbc_stream_t stream);
 int lbc_u8nhwc_to_input(const unsigned char* image_nhwc, void* xp, int xp_bf16, int N, int C, int H, int W, int normalize,
                         lbc_stream_t stream);

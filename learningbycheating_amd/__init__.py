@@ -20,6 +20,10 @@ __version__ = "0.1.0"
 #:         each tensor's largest entry both, cosine 0.9995 both; profiles/r03_run10_bf16_grad_vs_autocast.txt,
 #:         tests/test_model.py::test_bf16_gradients_match_autocast_reference) -- the tolerance is what bf16 costs, not what this
 #:         implementation adds; bf16 cannot meet 1e-3.
-WAYPOINT_TOLERANCE = {"fp32": 1e-3, "bf16": 3e-2, "bf16_mfma": 3e-2}
+#:   bf16x3: split-bf16 convolution operands (hi*hi + hi*lo + lo*hi on the bf16 MFMA, f32 tensors; stem, BatchNorm, head, loss and
+#:         Adam exact f32): the north-star bar, max <= 1e-3 and mean <= 1e-4 against the f32 oracle (measured on MI355X at batch 256:
+#:         r34 160x384 eval max 4.2e-4 / mean 2.8e-5, train 5.6e-4 / 2.4e-5; r18 bird-view max 1.5e-4 / mean 8.9e-6;
+#:         tests/test_precision_bf16x3.py::test_bf16x3_forward_parity_at_bench_batch_256).
+WAYPOINT_TOLERANCE = {"fp32": 1e-3, "bf16": 3e-2, "bf16_mfma": 3e-2, "bf16x3": 1e-3}
 #: ... and the mean absolute deviation over all predicted waypoint coordinates of a batch
-WAYPOINT_MEAN_TOLERANCE = {"fp32": 1e-4, "bf16": 4e-3, "bf16_mfma": 4e-3}
+WAYPOINT_MEAN_TOLERANCE = {"fp32": 1e-4, "bf16": 4e-3, "bf16_mfma": 4e-3, "bf16x3": 1e-4}

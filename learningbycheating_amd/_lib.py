@@ -14,7 +14,7 @@ _lib = None
 c_void_p, c_int, c_float, c_size_t, c_char_p = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p
 
 
-ABI_VERSION = 200     # include/lbc_hip.h LBC_HIP_ABI_VERSION: load() refuses a library that answers anything else
+ABI_VERSION = 201    # include/lbc_hip.h LBC_HIP_ABI_VERSION: load() refuses a library that answers anything else
 
 
 class ConvDesc(ctypes.Structure):

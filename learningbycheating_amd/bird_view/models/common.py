@@ -103,7 +103,9 @@ class PolicyBase(ResnetBase):
     #: "fp32" (default, the parity path: exact-f32 MFMA everywhere); "bf16" = mixed precision as in BASELINE.json config 3
     #: (convolution MFMA operands and the activations / activation gradients stored in HBM are bf16; f32 accumulation,
     #: f32 master weights, gradients, BatchNorm statistics, soft-argmax, loss and Adam); "bf16_mfma" = only the MFMA
-    #: operands are rounded to bf16, every tensor stays f32.  Set before the first forward.
+    #: operands are rounded to bf16, every tensor stays f32; "bf16x3" = every convolution but the stem multiplies split-bf16
+    #: operands (hi*hi + hi*lo + lo*hi on the bf16 MFMA, f32 accumulation: ~f32 accuracy), every tensor stays f32 and the
+    #: stem, BatchNorm, head, loss and Adam are exact f32.  Set before the first forward.
     precision = "fp32"
 
     def _finish_init(self):
@@ -133,7 +135,7 @@ class PolicyBase(ResnetBase):
 
     def _engine_for(self, image, with_grads):
         n, c, h, w = image.shape
-        prec = {"fp32": 0, "bf16_mfma": 1, "bf16": 2}[self.precision]
+        prec = {"fp32": 0, "bf16_mfma": 1, "bf16": 2, "bf16x3": 3}[self.precision]
         key = (h, w, str(image.device), prec)
         eng = self._engines.get(key)
         if eng is None or eng.max_batch < n:

@@ -33,6 +33,9 @@ static bool desc_ok(const lbc_conv_desc* d, const char* who)
 }
 #define LBC_DESC(d, who) do { if (!desc_ok((d), (who))) return LBC_EINVAL; } while (0)
 
+// lbc_conv_desc.bf16 = 4 (split bf16, "bf16x3") reads f32 tensors; every other mode >= 2 means bf16 tensors, as before
+static int act_bf16_mode(int m) { return m >= 2 && m != 4; }
+
 static IgemmArgs conv_args(const lbc_conv_desc* d)
 {
     IgemmArgs a;
@@ -40,7 +43,7 @@ static IgemmArgs conv_args(const lbc_conv_desc* d)
     a.N = d->N; a.H = d->H; a.W = d->W; a.C = d->C; a.K = d->K;
     a.KH = d->KH; a.KW = d->KW; a.S = d->S; a.P = d->P;
     a.relu = d->relu;
-    a.bf16 = d->bf16 != 0; a.act_bf16 = d->bf16 >= 2; a.w_bf16 = d->bf16 == 3;
+    a.bf16 = d->bf16 != 0; a.act_bf16 = act_bf16_mode(d->bf16); a.w_bf16 = d->bf16 == 3; a.x3 = d->bf16 == 4;
     a.split_ws = static_cast<float*>(d->split_workspace); a.split_ws_floats = (long long)(d->split_workspace_bytes / 4);
     return a;
 }
@@ -74,7 +77,8 @@ static int conv_dgrad_impl(const lbc_conv_desc* d, const void* dy, const void* w
     const int OW = (d->W + 2 * d->P - d->KW) / d->S + 1;
     IgemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.x = dy; a.w = w; a.y = dx; a.resid = resid; a.bias = bias; a.relu = relu; a.bf16 = d->bf16 != 0; a.act_bf16 = d->bf16 >= 2; a.w_bf16 = d->bf16 == 3;
+    a.x = dy; a.w = w; a.y = dx; a.resid = resid; a.bias = bias; a.relu = relu; a.bf16 = d->bf16 != 0; a.act_bf16 = act_bf16_mode(d->bf16);
+    a.w_bf16 = d->bf16 == 3; a.x3 = d->bf16 == 4;
     a.pre_scale = pre_scale; a.pre_shift = pre_shift; a.pre_relu = pre_relu;
     a.split_ws = static_cast<float*>(d->split_workspace); a.split_ws_floats = (long long)(d->split_workspace_bytes / 4);
     a.N = d->N; a.H = OH; a.W = OW; a.C = d->K;
@@ -163,7 +167,7 @@ static WgradArgs conv_wgrad_args(const lbc_conv_desc* d)
     a.CP = d->K;
     a.H = d->H; a.W = d->W; a.CQ = d->C;
     a.KH = d->KH; a.KW = d->KW; a.S = d->S; a.P = d->P;
-    a.bf16 = d->bf16 != 0; a.act_bf16 = d->bf16 >= 2;
+    a.bf16 = d->bf16 != 0; a.act_bf16 = act_bf16_mode(d->bf16); a.x3 = d->bf16 == 4;
     a.nsplit = lbc_wgrad_pick_split(a);
     return a;
 }
@@ -240,7 +244,7 @@ static WgradArgs deconv_wgrad_args(const lbc_conv_desc* d)
     a.N = d->N; a.OH = d->H; a.OW = d->W; a.CP = d->C;
     a.H = 2 * d->H; a.W = 2 * d->W; a.CQ = d->K;
     a.KH = 3; a.KW = 3; a.S = 2; a.P = 1;
-    a.bf16 = d->bf16 != 0; a.act_bf16 = d->bf16 >= 2;
+    a.bf16 = d->bf16 != 0; a.act_bf16 = act_bf16_mode(d->bf16); a.x3 = d->bf16 == 4;
     a.nsplit = lbc_wgrad_pick_split(a);
     return a;
 }

@@ -1,5 +1,6 @@
 // Implicit-GEMM convolution for gfx950 (MI355X): exact f32 on v_mfma_f32_32x32x2_f32, or bf16 operands (f32 / bf16
-// tensors, f32 / bf16 weight copies) on v_mfma_f32_32x32x16_bf16.  One kernel template serves
+// tensors, f32 / bf16 weight copies; or split hi + lo bf16 operands on f32 tensors, "bf16x3") on v_mfma_f32_32x32x16_bf16.
+// One kernel template serves
 //   * nn.Conv2d forward                (reference bird_view/models/resnet.py:15-22,102)
 //   * nn.Conv2d input gradient         (autograd of the same call sites)
 //   * nn.ConvTranspose2d forward       (reference bird_view/models/image.py:39,42,45)
@@ -39,10 +40,15 @@ namespace {
 // loaded-L2 round trip (measured 1.5 us per chunk = 7x its MFMA time at PF = 1), so the all-bf16 kernels run PF = 2.
 // BKV = channels per depth chunk (0: 64 for the bf16 paths, 32 for f32).  The 64 x 64 tiles of small launches take 128: a chunk
 // there is 4 MFMAs per wave, so its cost is the barrier and the load round trip, and twice the depth halves their number.
-template <int BM, int BN, bool WMAJOR, int MODE, bool BF16, typename AT, typename WT, int PF, int BKV = 0>
+// X3 (split bf16, "bf16x3"; BF16 on f32 tensors and f32 weights only): every f32 operand v is written to LDS as hi = bf16(v) and
+// lo = bf16(v - hi) (the subtraction is exact), after the on-load affine and the zero mask, so a masked element is 0 in both planes.
+// An LDS row holds [hi: BK][lo: BK][pad 8] (272-byte rows, the same bank pattern as the 144-byte ones) and each fragment pair costs
+// three MFMAs into the one f32 accumulator, lo*hi + hi*lo first and hi*hi last; lo*lo (~2^-16 relative) is dropped.
+template <int BM, int BN, bool WMAJOR, int MODE, bool BF16, typename AT, typename WT, int PF, int BKV = 0, bool X3 = false>
 __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a)
 {
     static_assert(!BF16 || WMAJOR, "the bf16 path needs depth-contiguous weights");
+    static_assert(!X3 || (BF16 && !Act<AT>::kBf16 && !Act<WT>::kBf16), "the split path reads f32 tensors and f32 weights");
     static_assert(!Act<AT>::kBf16 || BF16, "bf16 activations need the bf16 MFMA path");
     static_assert(!Act<WT>::kBf16 || BF16, "bf16 weights need the bf16 MFMA path");
     constexpr bool ABF = Act<AT>::kBf16;
@@ -52,7 +58,8 @@ __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a
     using areg_t = typename std::conditional<ABF, bf16x8, f32x4>::type;   // one 16-byte activation load
     using lds_t = typename std::conditional<BF16, __bf16, float>::type;
     constexpr int BK = BKV ? BKV : (BF16 ? 64 : 32);      // channels per depth chunk
-    constexpr int LDK = BK + (BF16 ? 8 : 4);   // padded LDS row (elements): 144-byte (or 272-byte) rows -> conflict-free b128 reads
+    constexpr int LDK = (X3 ? 2 * BK : BK) + (BF16 ? 8 : 4);   // padded LDS row (elements): 144-byte (or 272-byte) rows -> conflict-free b128 reads
+    constexpr int LO = X3 ? BK : 0;         // offset of the lo plane within a row (X3)
     constexpr int SEGS = BK / BEL;          // 16-byte segments per weight-tile row
     constexpr int RPP = 256 / SEGS;         // tile rows staged per pass of the 256 threads
     constexpr int WM = 2, WN = 2;
@@ -68,6 +75,8 @@ __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a
 
     __shared__ __attribute__((aligned(16))) lds_t sA[2][BM * LDK];
     __shared__ __attribute__((aligned(16))) lds_t sB[2][SB];
+    // budget: one workgroup per CU at most 160 KB (X3, 128 x 128: 2 buffers x (128 + 128) rows x 272 B = 136 KB)
+    static_assert(sizeof(lds_t) * 2 * (BM * LDK + SB) <= 160 * 1024, "conv_igemm: LDS");
     __shared__ int sTap[16];
     __shared__ int sNTap;
     __shared__ int sOpix[BM];   // output pixel of every tile row (strided / phase launches; dense launches use m itself)
@@ -224,7 +233,32 @@ __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a
         }
         if (it >= 0) {
             const int buf = it & 1;
-            if constexpr (BF16) {
+            if constexpr (X3) {
+#pragma unroll
+                for (int g = 0; g < BK / 16; ++g) {
+                    bf16x8 ah[MT], al[MT], bh[NT], bl[NT];
+#pragma unroll
+                    for (int i = 0; i < MT; ++i) {
+                        const lds_t* src = &sA[buf][((wm * MT + i) * 32 + l31) * LDK + g * 16 + kh * 8];
+                        ah[i] = *reinterpret_cast<const bf16x8*>(src);
+                        al[i] = *reinterpret_cast<const bf16x8*>(src + LO);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        const lds_t* src = &sB[buf][((wn * NT + j) * 32 + l31) * LDK + g * 16 + kh * 8];
+                        bh[j] = *reinterpret_cast<const bf16x8*>(src);
+                        bl[j] = *reinterpret_cast<const bf16x8*>(src + LO);
+                    }
+#pragma unroll
+                    for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                        for (int nj = 0; nj < NT; ++nj) {
+                            acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[nj], acc[mi][nj], 0, 0, 0);
+                            acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[nj], acc[mi][nj], 0, 0, 0);
+                            acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[nj], acc[mi][nj], 0, 0, 0);
+                        }
+                }
+            } else if constexpr (BF16) {
 #pragma unroll
                 for (int g = 0; g < BK / 16; ++g) {
                     bf16x8 af[MT], bf[NT];
@@ -286,7 +320,8 @@ __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a
                     f32x4 v = ra[SS][j] * lps[SS][0] + lpt[SS][0];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = aok[SS][j] ? fmaxf(v[e], relu_floor) : 0.f;
-                    if constexpr (BF16) *reinterpret_cast<bf16x4*>(dst) = __builtin_convertvector(v, bf16x4);
+                    if constexpr (X3) split_store(dst, LO, v);
+                    else if constexpr (BF16) *reinterpret_cast<bf16x4*>(dst) = __builtin_convertvector(v, bf16x4);
                     else                *reinterpret_cast<f32x4*>(dst) = v;
                 }
             }
@@ -294,6 +329,8 @@ __global__ __launch_bounds__(256, PF == 2 ? 2 : 1) void conv_igemm_k(IgemmArgs a
             for (int j = 0; j < RB; ++j) {
                 if constexpr (WBF) {
                     *reinterpret_cast<bf16x8*>(&sB[buf][(arow + RPP * j) * LDK + seg * 8]) = rb[SS][j];
+                } else if constexpr (X3) {
+                    split_store(&sB[buf][(arow + RPP * j) * LDK + seg * 4], LO, rb[SS][j]);
                 } else if constexpr (BF16) {
                     *reinterpret_cast<bf16x4*>(&sB[buf][(arow + RPP * j) * LDK + seg * 4]) = __builtin_convertvector(rb[SS][j], bf16x4);
                 } else if (WMAJOR) {
@@ -464,6 +501,9 @@ int launch_cfg(const IgemmArgs& a, int wmajor, int mode, hipStream_t s)
     } else if (a.act_bf16) {
         if (mode == 0) hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 0, true, __bf16, float, 1>), grid, dim3(256), 0, s, a);
         else           hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 1, true, __bf16, float, 1>), grid, dim3(256), 0, s, a);
+    } else if (a.x3) {
+        if (mode == 0) hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 0, true, float, float, 1, 0, true>), grid, dim3(256), 0, s, a);
+        else           hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 1, true, float, float, 1, 0, true>), grid, dim3(256), 0, s, a);
     } else if (a.bf16) {
         if (mode == 0) hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 0, true, float, float, 1>), grid, dim3(256), 0, s, a);
         else           hipLaunchKernelGGL((conv_igemm_k<BM, BN, true, 1, true, float, float, 1>), grid, dim3(256), 0, s, a);
@@ -553,6 +593,7 @@ int lbc_igemm_launch(const IgemmArgs& a, int wmajor, int mode, int cfg, hipStrea
     LBC_REQUIRE(!a.bf16 || wmajor, "igemm: the bf16 path needs depth-contiguous weights (transpose first)");
     LBC_REQUIRE(!a.act_bf16 || a.bf16, "igemm: bf16 activations need bf16 = 1");
     LBC_REQUIRE(!a.w_bf16 || a.act_bf16, "igemm: bf16 weight copies are used with bf16 activations only");
+    LBC_REQUIRE(!a.x3 || (a.bf16 && !a.act_bf16), "igemm: split-bf16 operands need bf16 = 1 on f32 tensors");
     LBC_REQUIRE(cfg >= kLbcCfgGlds || a.K % kCfgBN[cfg] == 0, "igemm: output channels %d not a multiple of the tile", a.K);
     LBC_REQUIRE(a.KH * a.KW <= 16, "igemm: too many taps");
     LBC_REQUIRE(a.S == 1 || a.S == 2, "igemm: stride %d unsupported", a.S);
@@ -578,6 +619,7 @@ int lbc_igemm_launch(const IgemmArgs& a, int wmajor, int mode, int cfg, hipStrea
                         : cfg >= kLbcCfgHdma ? (mode == 0 ? "conv_hdma_gather" : "conv_hdma_transposed")
                         : cfg >= kLbcCfgGlds ? (mode == 0 ? "conv_glds_gather" : "conv_glds_transposed")
                         : halo ? (mode == 0 ? "conv_halo_gather" : "conv_halo_transposed")
+                        : a.x3 ? (mode == 0 ? "conv_igemm_x3_gather" : "conv_igemm_x3_transposed")
                                : (mode == 0 ? "conv_igemm_gather" : "conv_igemm_transposed");
     LbcProfScope prof(pname, 2.0 * a.M * nph * a.K * (double)a.C * taps,
                       // (+ the side tensors of the fused BatchNorm-backward reduce: the pre-BatchNorm activation, and in the tensor-masked form the ReLU output)

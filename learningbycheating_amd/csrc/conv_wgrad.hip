@@ -204,15 +204,20 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(WgradArgs a, int rows_per_
 // banks, and a row is 36 dwords, so lanes of a group that differ only in their channel group (8 rows = 288 dwords = 0
 // mod 32) collide: the micro-tile index therefore puts KB channel-group bits and 4-KB pixel-group bits into the low 4
 // lane bits (KB = 1: f32 input conflict-free, bf16 input 2-way; loads still cover whole 128-byte lines per wave).
-template <int BP, int BQ, typename AT, int KB>
+// X3 (split bf16, f32 input only): each transposed column is written as hi = bf16(v) and lo = bf16(v - hi), rows [hi: 64][lo: 64][pad 8]
+// (272 B: the same bank pattern for the staging writes and the fragment reads as 144 B), and each fragment pair costs three MFMAs
+// (lo*hi, hi*lo, then hi*hi) into the f32 accumulator; see conv_igemm.hip.
+template <int BP, int BQ, typename AT, int KB, bool X3 = false>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_k(WgradArgs a, int rows_per_split)
 {
     constexpr bool ABF = Act<AT>::kBf16;
+    static_assert(!X3 || !ABF, "the split path reads f32 tensors");
     // channels per load: 16-byte loads, except bf16 input on the 64-wide tiles (8-byte loads keep all 256 threads staging)
     constexpr int CH = (ABF && BP >= 128) ? 8 : 4;
     using areg_t = typename std::conditional<ABF, typename std::conditional<CH == 8, bf16x8, bf16x4>::type, f32x4>::type;
     constexpr int BRH = 64;                 // pixels per chunk
-    constexpr int LD = BRH + 8;             // padded LDS row (bf16 elements) = 144 bytes
+    constexpr int LD = (X3 ? 2 * BRH : BRH) + 8;   // padded LDS row (bf16 elements) = 144 bytes (X3: 272)
+    constexpr int LO = X3 ? BRH : 0;               // offset of the lo plane within a row (X3)
     constexpr int WM = 2, WN = 2;
     constexpr int MT = BP / WM / 32, NT = BQ / WN / 32;
     constexpr int CGP = BP / CH, CGQ = BQ / CH;          // channel groups
@@ -220,6 +225,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_k(WgradArgs a, int rows_p
     constexpr int NP = (TP_ + 255) / 256, NQ = (TQ_ + 255) / 256;   // micro-tiles per thread
     __shared__ __attribute__((aligned(16))) __bf16 sP[2][BP * LD];
     __shared__ __attribute__((aligned(16))) __bf16 sQ[2][BQ * LD];
+    // budget: X3 on 128 x 128 tiles: 2 buffers x (128 + 128) rows x 272 B = 136 KB, one workgroup per CU
+    static_assert(sizeof(__bf16) * 2 * (BP + BQ) * LD <= 160 * 1024, "conv_wgrad: LDS");
 
     const AT* pin = static_cast<const AT*>(a.p);
     const AT* qin = static_cast<const AT*>(a.q);
@@ -335,7 +342,33 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_k(WgradArgs a, int rows_p
                 while (qy[t] >= a.OH) { qy[t] -= a.OH; ++qn[t]; }
             }
         }
-        if (ch >= 0) {
+        if (ch >= 0 && X3) {
+            const int buf = ch & 1;
+#pragma unroll
+            for (int g = 0; g < BRH / 16; ++g) {
+                bf16x8 ah[MT], al[MT], bh[NT], bl[NT];
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    const __bf16* src = &sP[buf][((wm * MT + i) * 32 + l31) * LD + g * 16 + kh * 8];
+                    ah[i] = *reinterpret_cast<const bf16x8*>(src);
+                    al[i] = *reinterpret_cast<const bf16x8*>(src + LO);
+                }
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const __bf16* src = &sQ[buf][((wn * NT + j) * 32 + l31) * LD + g * 16 + kh * 8];
+                    bh[j] = *reinterpret_cast<const bf16x8*>(src);
+                    bl[j] = *reinterpret_cast<const bf16x8*>(src + LO);
+                }
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                    }
+            }
+        } else if (ch >= 0) {
             const int buf = ch & 1;
 #pragma unroll
             for (int g = 0; g < BRH / 16; ++g) {
@@ -372,7 +405,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_k(WgradArgs a, int rows_p
 #pragma unroll
                     for (int c = 0; c < CH; ++c) {
                         const f32x4 col = {v[0][c], v[1][c], v[2][c], v[3][c]};   // channel c of the 4 pixels
-                        *reinterpret_cast<bf16x4*>(&sP[buf][(cg * CH + c) * LD + pg * 4]) = __builtin_convertvector(col, bf16x4);
+                        if constexpr (X3) split_store(&sP[buf][(cg * CH + c) * LD + pg * 4], LO, col);
+                        else *reinterpret_cast<bf16x4*>(&sP[buf][(cg * CH + c) * LD + pg * 4]) = __builtin_convertvector(col, bf16x4);
                     }
                 }
             }
@@ -393,7 +427,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_k(WgradArgs a, int rows_p
 #pragma unroll
                     for (int c = 0; c < CH; ++c) {
                         const f32x4 col = {v[0][c], v[1][c], v[2][c], v[3][c]};
-                        *reinterpret_cast<bf16x4*>(&sQ[buf][(cg * CH + c) * LD + pg * 4]) = __builtin_convertvector(col, bf16x4);
+                        if constexpr (X3) split_store(&sQ[buf][(cg * CH + c) * LD + pg * 4], LO, col);
+                        else *reinterpret_cast<bf16x4*>(&sQ[buf][(cg * CH + c) * LD + pg * 4]) = __builtin_convertvector(col, bf16x4);
                     }
                 }
             }
@@ -501,6 +536,7 @@ int lbc_wgrad_launch(const WgradArgs& a, hipStream_t s)
     LBC_REQUIRE(a.CP % 64 == 0 && a.CQ % 64 == 0, "wgrad: channels (%d,%d) must be multiples of 64", a.CP, a.CQ);
     LBC_REQUIRE(a.nsplit >= 1, "wgrad: nsplit %d", a.nsplit);
     LBC_REQUIRE(!a.act_bf16 || a.bf16, "wgrad: bf16 operands need bf16 = 1");
+    LBC_REQUIRE(!a.x3 || (a.bf16 && !a.act_bf16), "wgrad: split-bf16 operands need bf16 = 1 on f32 tensors");
     const long long M = (long long)a.N * a.OH * a.OW;
     LBC_REQUIRE(M > 0 && M * a.CP < (1ll << 31) && (long long)a.N * a.H * a.W * a.CQ < (1ll << 31), "wgrad: bad tensor size");
     if (lbc_wgrad_tr_eligible(a)) return lbc_wgrad_tr_launch(a, s);
@@ -508,7 +544,7 @@ int lbc_wgrad_launch(const WgradArgs& a, hipStream_t s)
     const int br = a.bf16 ? 64 : BR;
     const long long chunks = (M + br - 1) / br;
     const int rows_per_split = (int)((chunks + a.nsplit - 1) / a.nsplit) * br;
-    LbcProfScope prof("conv_wgrad", 2.0 * M * a.CP * (double)a.CQ * a.KH * a.KW,
+    LbcProfScope prof(a.x3 ? "conv_wgrad_x3" : "conv_wgrad", 2.0 * M * a.CP * (double)a.CQ * a.KH * a.KW,
                       (a.act_bf16 ? 2.0 : 4.0) * ((double)M * a.CP + (double)a.N * a.H * a.W * a.CQ) +
                           4.0 * (double)a.nsplit * a.CP * a.KH * a.KW * a.CQ, s);
     const int bt = big_tile(a) ? 128 : 64;
@@ -518,6 +554,9 @@ int lbc_wgrad_launch(const WgradArgs& a, hipStream_t s)
     if (a.act_bf16) {
         if (big_tile(a)) hipLaunchKernelGGL((conv_wgrad_bf16_k<128, 128, __bf16, 1>), grid, dim3(256), 0, s, a, rows_per_split);
         else             hipLaunchKernelGGL((conv_wgrad_bf16_k<64, 64, __bf16, 2>), grid, dim3(256), 0, s, a, rows_per_split);
+    } else if (a.x3) {
+        if (big_tile(a)) hipLaunchKernelGGL((conv_wgrad_bf16_k<128, 128, float, 2, true>), grid, dim3(256), 0, s, a, rows_per_split);
+        else             hipLaunchKernelGGL((conv_wgrad_bf16_k<64, 64, float, 2, true>), grid, dim3(256), 0, s, a, rows_per_split);
     } else if (a.bf16) {
         if (big_tile(a)) hipLaunchKernelGGL((conv_wgrad_bf16_k<128, 128, float, 2>), grid, dim3(256), 0, s, a, rows_per_split);
         else             hipLaunchKernelGGL((conv_wgrad_bf16_k<64, 64, float, 2>), grid, dim3(256), 0, s, a, rows_per_split);

@@ -77,6 +77,8 @@ Net::Net(const lbc_net_desc& d) : d_(d)
     side_allowed_ = !lbc_opt_on(kOptNoSideStream);
     bf16_ = d.precision >= 1;
     act_bf16_ = d.precision == 2;
+    x3_ = d.precision == 3;
+    stem_bf16_ = bf16_ && !x3_;
     defer_wgrad_ = act_bf16_;
     if (defer_wgrad_) side_allowed_ = false;      // nothing is left for a side stream: the deferred launches fill the chip by themselves
     if (bf16_) dgrad_wt_ = true;   // the bf16 tiles are [row][depth] only: every weight operand must be depth-contiguous
@@ -178,7 +180,7 @@ Net::Net(const lbc_net_desc& d) : d_(d)
         WgradArgs a;
         memset(&a, 0, sizeof(a));
         a.N = N; a.OH = OH; a.OW = OW; a.CP = CP; a.H = Hq; a.W = Wq; a.CQ = CQ; a.KH = k; a.KW = k; a.S = s; a.P = p;
-        a.bf16 = bf16_; a.act_bf16 = act_bf16_;      // the split policy depends on the kernel that will run
+        a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;      // the split policy depends on the kernel that will run
         return (size_t)lbc_wgrad_pick_split(a) * CP * k * k * CQ;
     };
     for (const Block& b : blocks_) {
@@ -188,7 +190,7 @@ Net::Net(const lbc_net_desc& d) : d_(d)
     }
     for (int i = 0; i < 3; ++i)
         wg = std::max(wg, wg_need((int)NB, dec_[i].H, dec_[i].W, dec_[i].Cin, 2 * dec_[i].H, 2 * dec_[i].W, dec_[i].Cout, 3, 2, 1));
-    wg = std::max(wg, (size_t)lbc_stem_wgrad_split((int)NB, H0, W0, Cin, bf16_) * 64 * 49 * Cin);
+    wg = std::max(wg, (size_t)lbc_stem_wgrad_split((int)NB, H0, W0, Cin, stem_bf16_) * 64 * 49 * Cin);
     if (defer_wgrad_) {
         // a stage's 3x3 / stride-1 convolutions share one shape: the slabs of their grouped launch, and one dY slot per convolution
         for (size_t li = 0; li < stage_first_block_.size(); ++li) {
@@ -301,7 +303,7 @@ int Net::conv_fwd(const Conv& c, const float* x, int N, bool stats, int* rows, h
     a.OH = c.OH; a.OW = c.OW; a.K = c.Cout;
     a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
     a.M = N * c.OH * c.OW; a.LH = c.OH; a.LW = c.OW; a.ostep = 1;
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_;
+    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
     if (act_bf16_) { a.w = W(c.wn); a.w_bf16 = 1; }
     split_scratch(a);
     const int cfg = lbc_igemm_pick_for(a, 0);
@@ -464,8 +466,8 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
     const float m3[3] = {0.485f, 0.456f, 0.406f}, s3[3] = {0.229f, 0.224f, 0.225f};
     for (int i = 0; i < 3; ++i) { nc.mean[i] = m3[i]; nc.stdv[i] = s3[i]; }
     // bf16 modes: the padded image is bf16 too
-    if (image_u8) LBC_TRY(lbc_prep_input_u8(static_cast<const unsigned char*>(image), W(xp_), bf16_, N, Cin, H0, W0, nc, s));
-    else          LBC_TRY(lbc_prep_input(static_cast<const float*>(image), W(xp_), bf16_, N, Cin, H0, W0, nc, s));
+    if (image_u8) LBC_TRY(lbc_prep_input_u8(static_cast<const unsigned char*>(image), W(xp_), stem_bf16_, N, Cin, H0, W0, nc, s));
+    else          LBC_TRY(lbc_prep_input(static_cast<const float*>(image), W(xp_), stem_bf16_, N, Cin, H0, W0, nc, s));
     // derived from the weights alone: skipped when the caller declared them frozen and an eval-mode forward has derived them already
     const bool reuse = frozen_ && derived_valid_ && !tr;
     if (act_bf16_ && !reuse) LBC_TRY(weight_prep(s));   // the caller's optimizer may have stepped: refresh the bf16 weight copies
@@ -474,8 +476,8 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
 
     // resnet.py:148-152: conv1 -> bn1 -> relu -> maxpool
     StemArgs st;
-    st.xp = W(xp_); st.xp_bf16 = bf16_; st.w = P(stem_w_); st.y = W(y0_); st.stats = tr ? W(partial_) : nullptr;
-    st.N = N; st.H = H0; st.W = W0; st.Cin = Cin; st.act_bf16 = act_bf16_; st.bf16 = bf16_;
+    st.xp = W(xp_); st.xp_bf16 = stem_bf16_; st.w = P(stem_w_); st.y = W(y0_); st.stats = tr ? W(partial_) : nullptr;
+    st.N = N; st.H = H0; st.W = W0; st.Cin = Cin; st.act_bf16 = act_bf16_; st.bf16 = stem_bf16_;
     LBC_TRY(lbc_stem_fwd(st, s));
     if (tr) LBC_TRY(bn_finalize(stem_bn_, lbc_stem_rows(st), (long long)N * (H0 / 2) * (W0 / 2), N, train, s));
     PoolFwdArgs pf;
@@ -575,7 +577,7 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
         } else if (bf16_) {
             // w[Cin][T][Cout] -> wt[Cout][T][Cin]: depth-contiguous for the bf16 tiles
             LBC_TRY(lbc_weight_transpose(P(D.w), W(wt_), D.Cin, 9, D.Cout, s));
-            a.w = W(wt_); a.bf16 = 1; wmajor = 1;
+            a.w = W(wt_); a.bf16 = 1; a.x3 = x3_; wmajor = 1;
         }
         a.nphase = 4;                       // the four output-parity phases in one launch; statistics rows ph * per + tile
         int cfg = lbc_igemm_pick(a.M, a.K);
@@ -727,7 +729,7 @@ int Net::flush_wgrads(int N, hipStream_t s)
         memset(&a, 0, sizeof(a));
         a.p = pi.dy; a.q = pi.x;
         if (pi.pre) { a.q_scale = W(pi.pre->scale); a.q_shift = W(pi.pre->shift); a.q_relu = 1; }
-        a.bf16 = bf16_; a.act_bf16 = act_bf16_;
+        a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
         a.N = N; a.OH = c.OH; a.OW = c.OW; a.CP = c.Cout; a.H = c.H; a.W = c.W; a.CQ = c.Cin;
         a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
         if (!lbc_wgrad_tr_eligible(a)) {
@@ -773,7 +775,7 @@ int Net::conv_wgrad_pre(const Conv& c, const float* x, const BN* pre, const floa
     memset(&a, 0, sizeof(a));
     a.p = dy; a.q = x; a.partial = W(wg_partial_);
     if (pre) { a.q_scale = W(pre->scale); a.q_shift = W(pre->shift); a.q_relu = 1; }
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_;
+    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
     a.N = N; a.OH = c.OH; a.OW = c.OW; a.CP = c.Cout;
     a.H = c.H; a.W = c.W; a.CQ = c.Cin;
     a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
@@ -799,7 +801,7 @@ int Net::conv_dgrad(const Conv& c, const float* dy, const float* resid, float* d
     a.OH = c.H; a.OW = c.W; a.K = c.Cin;
     a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
     int wmajor = 0;
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_;
+    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
     if (act_bf16_) {
         a.w = W(c.wt); a.w_bf16 = 1; wmajor = 1;
     } else if (dgrad_wt_ && (c.k == 3 || bf16_)) {
@@ -1022,7 +1024,7 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
             wa.p_scale = W(D.bn.scale); wa.p_shift = W(D.bn.shift);
             wa.N = N; wa.OH = D.H; wa.OW = D.W; wa.CP = D.Cin;
             wa.H = 2 * D.H; wa.W = 2 * D.W; wa.CQ = D.Cout; wa.KH = 3; wa.KW = 3; wa.S = 2; wa.P = 1;
-            wa.bf16 = bf16_; wa.act_bf16 = act_bf16_;
+            wa.bf16 = bf16_; wa.act_bf16 = act_bf16_; wa.x3 = x3_;
             wa.nsplit = lbc_wgrad_pick_split(wa);
             if ((size_t)wa.nsplit * D.Cin * 9 * D.Cout > wg_floats_) wa.nsplit = (int)std::max<size_t>(1, wg_floats_ / ((size_t)D.Cin * 9 * D.Cout));
             if (wa.nsplit == 1) wa.partial = G(D.w);
@@ -1035,7 +1037,7 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
             a.N = N; a.H = 2 * D.H; a.W = 2 * D.W; a.C = D.Cout;
             a.OH = D.H; a.OW = D.W; a.K = D.Cin; a.KH = 3; a.KW = 3; a.S = 2; a.P = 1;
             a.M = N * D.H * D.W; a.LH = D.H; a.LW = D.W; a.ostep = 1;
-            a.bf16 = bf16_; a.act_bf16 = act_bf16_;
+            a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
             if (act_bf16_) { a.w = W(D.wn); a.w_bf16 = 1; }
             LBC_TRY(lbc_igemm_launch(a, 1, 0, act_bf16_ ? lbc_igemm_pick_for(a, 0) : lbc_igemm_pick(a.M, a.K), s));   // F = d bn(x)
             // BatchNorm backward; for the first decoder stage only the 512 trunk channels carry on
@@ -1082,7 +1084,7 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
         LBC_TRY(bn_bwd_finalize(f, s));
         StemWgradArgs sw;
         memset(&sw, 0, sizeof(sw));
-        if (lbc_stem_wgrad_fuses_bn_bwd(d_.in_channels, bf16_)) {
+        if (lbc_stem_wgrad_fuses_bn_bwd(d_.in_channels, stem_bf16_)) {
             // the apply pass dx = A (g - k1 - xhat k2) feeds only the stem's weight gradient (nothing lies below conv1): that kernel
             // forms it while it stages g (-1 read and -1 write of the largest activation, +1 read of y0 there)
             sw.bn_y = W(y0_); sw.bn_coefA = W(stem_bn_.cA); sw.bn_coefB = W(stem_bn_.cB); sw.bn_coefD = W(stem_bn_.cD);
@@ -1095,9 +1097,9 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
             ap.dx = W(g0_); ap.pixels = pix; ap.C = 64; ap.Cout = 64; ap.act_bf16 = act_bf16_;
             LBC_TRY(lbc_bn_bwd_apply(ap, s));
         }
-        sw.xp = W(xp_); sw.xp_bf16 = bf16_; sw.dy = W(g0_); sw.partial = W(wg_partial_);
-        sw.N = N; sw.H = H0; sw.W = W0; sw.Cin = d_.in_channels; sw.act_bf16 = act_bf16_; sw.bf16 = bf16_;
-        sw.nsplit = lbc_stem_wgrad_split(N, H0, W0, d_.in_channels, bf16_);
+        sw.xp = W(xp_); sw.xp_bf16 = stem_bf16_; sw.dy = W(g0_); sw.partial = W(wg_partial_);
+        sw.N = N; sw.H = H0; sw.W = W0; sw.Cin = d_.in_channels; sw.act_bf16 = act_bf16_; sw.bf16 = stem_bf16_;
+        sw.nsplit = lbc_stem_wgrad_split(N, H0, W0, d_.in_channels, stem_bf16_);
         LBC_TRY(lbc_stem_wgrad(sw, s));
         LBC_TRY(lbc_splitk_reduce(sw.partial, sw.nsplit, (long long)64 * 49 * d_.in_channels, G(stem_w_), 0.f, s));
     }
@@ -1121,8 +1123,9 @@ int lbc_net_create(const lbc_net_desc* d, lbc_net** out)
     LBC_REQUIRE(d->H > 0 && d->W > 0 && d->H % 32 == 0 && d->W % 32 == 0, "net_create: image %dx%d must be a multiple of 32", d->H, d->W);
     LBC_REQUIRE(d->max_batch >= 1, "net_create: max_batch %d", d->max_batch);
     LBC_REQUIRE(!d->normalize || d->in_channels == 3, "net_create: ImageNet normalisation needs 3 channels");
-    LBC_REQUIRE(d->precision >= 0 && d->precision <= 2,
-                "net_create: precision %d unknown (0 = f32, 1 = bf16 MFMA operands, 2 = bf16 operands + bf16 activation storage)", d->precision);
+    LBC_REQUIRE(d->precision >= 0 && d->precision <= 3,
+                "net_create: precision %d unknown (0 = f32, 1 = bf16 MFMA operands, 2 = bf16 operands + bf16 activation storage, "
+                "3 = split-bf16 operands (bf16x3))", d->precision);
     LBC_REQUIRE((long long)d->max_batch * (d->H / 2) * (d->W / 2) * 64 < (1ll << 31), "net_create: batch too large for 32-bit indexing");
     *out = new lbc_net(*d);
     return LBC_OK;

@@ -125,6 +125,8 @@ private:
     size_t wt_ = 0;
     bool bf16_ = false;      // precision >= 1: bf16 MFMA operands in the convolution family
     bool act_bf16_ = false;  // precision 2: activations and activation gradients are stored as bf16 in HBM
+    bool x3_ = false;        // precision 3: split-bf16 operands (hi*hi + hi*lo + lo*hi) in the convolution family except the stem
+    bool stem_bf16_ = false; // bf16 operands in the input repack and the stem (precision 1 and 2; precision 3 keeps them exact f32)
     int weight_prep(hipStream_t s);
     bool conv_takes_glds(const Conv& c, int N, bool with_prologue = false) const;
     // synced: partial_ rows were all-reduced already by sync_rows() (several BatchNorms finalized from the same sums)

@@ -46,6 +46,15 @@ __device__ __forceinline__ bf16x4 lds_read_tr16(const __bf16* p)
     return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)p);
 }
 
+// Split-bf16 ("bf16x3") operand staging: four f32 values as hi = bf16(v) (RNE) at p and lo = bf16(v - hi) at p + lo_off.  v - hi is
+// exact in f32, so hi + lo carries 16 significant bits and hi*hi' + hi*lo' + lo*hi' reproduces the f32 product to ~2^-16.
+__device__ __forceinline__ void split_store(__bf16* p, int lo_off, f32x4 v)
+{
+    const bf16x4 hi = __builtin_convertvector(v, bf16x4);
+    *reinterpret_cast<bf16x4*>(p) = hi;
+    *reinterpret_cast<bf16x4*>(p + lo_off) = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
+}
+
 // V consecutive per-channel f32 parameters (V = 4 or 8) as a vector
 template <int V> struct ParamVec;
 template <> struct ParamVec<4> {

@@ -130,6 +130,7 @@ struct IgemmArgs {
     // range), f32 partial tiles [range][M][K] here and a second launch that sums them and does the epilogue (conv_hdmap.hip).
     float* split_ws;
     long long split_ws_floats;
+    int x3;               // 1: split-bf16 operands, hi*hi + hi*lo + lo*hi on the bf16 MFMA (requires bf16 = 1, f32 tensors and weights)
 };
 // true when the kernel a (cfg, wmajor, mode) launch takes implements IgemmArgs::bnb_*
 bool lbc_igemm_fuses_bn_bwd(const IgemmArgs& a, int wmajor, int mode, int cfg);
@@ -205,6 +206,7 @@ struct WgradArgs {
     int nsplit;
     int bf16;             // 1: bf16 MFMA operands (f32 accumulation)
     int act_bf16;         // 1: p / q are bf16 tensors (requires bf16 = 1)
+    int x3;               // 1: split-bf16 operands, three bf16 MFMAs per fragment pair (requires bf16 = 1 on f32 tensors)
 };
 int lbc_wgrad_pick_split(const WgradArgs& a);      // needs bf16 / act_bf16 set: the tap-fused kernel has its own split policy
 int lbc_wgrad_launch(const WgradArgs& a, hipStream_t s);

@@ -90,8 +90,9 @@ def main(argv=None):
     parser.add_argument("--lr", type=float, default=1e-4)
     parser.add_argument("--synthetic", type=int, default=2048)
     parser.add_argument("--iters_per_epoch", type=int, default=1000)
-    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma"], default="fp32",
-                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights")
+    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
+                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
+                             "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
     parsed = parser.parse_args(argv)
     if parsed.pretrained:
         raise SystemExit("--pretrained downloads ImageNet weights (reference resnet.py:175-178); no network here")

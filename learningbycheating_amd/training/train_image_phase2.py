@@ -91,8 +91,9 @@ def main(argv=None):
     parser.add_argument("--speed_noise", type=float, default=0.0)
     parser.add_argument("--lr", type=float, default=1e-4)
     parser.add_argument("--synthetic", type=int, default=20000, help="frames in the synthetic replay buffer")
-    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma"], default="fp32",
-                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights")
+    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
+                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
+                             "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
     parsed = parser.parse_args(argv)
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
