@@ -30,6 +30,9 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  * 200: lbc_conv_desc starts with struct_size, which every entry point checks (a descriptor from an older header, or one that was not
  *      initialised, is refused with LBC_EINVAL instead of being read past); lbc_adam_profile_elems.  Accepted: every struct_size from the
  *      ABI-200 layout (through split_workspace_bytes) up to the library's own sizeof -- fields appended later are optional for older hosts.
+ * 201: lbc_conv_desc.bf16 = 4 / lbc_net_desc.precision = 3.  Later, without a new number: lbc_adam_state, lbc_adam_state_bytes,
+ *      lbc_adam_step_guarded -- exports were only ADDED, every 201 host stays valid against this library, and a host that needs the
+ *      guarded step finds out with dlsym (the Python binding fails on the missing symbol when it declares its signatures).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -220,6 +223,32 @@ int lbc_phase2_weight(const lbc_camera* cam, const float* pred_sel, const float*
 typedef struct lbc_adam_chunk { float* p; const float* g; float* m; float* v; int n; int pad; } lbc_adam_chunk;
 int lbc_adam_step(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
                   double eps, double weight_decay, int step, lbc_stream_t stream);
+
+/* Guarded Adam: the same update behind a scan of the gradients for NaN / +-Inf, decided on the device -- a step whose
+ * gradients hold one non-finite element is skipped as a whole (p, m, v and the step count keep their bits) without the host
+ * ever looking.  The reference has no such guard: its phase-1 / phase-2 loss unprojects with 1 / y
+ * (training/train_image_phase1.py:43-64), and a waypoint on the horizon row turns every parameter into NaN.
+ * The step count lives in a device record owned by the caller: lbc_adam_state_bytes() bytes of device memory, 8-byte aligned,
+ * ZERO-filled once before the first call (a fresh optimizer), never written by the host while steps are in flight; to resume,
+ * upload a record whose `step` (and counters) carry the saved values and whose other fields are zero.  Counters are 64-bit.
+ * One call enqueues, in order: the scan (reads g once, raises scan_flag), one bookkeeping thread (bad = scan_flag, scan_flag = 0;
+ * clean: step += 1, skipped_in_a_row = 0, coefficients of the new step computed in double; bad: skipped_total += 1,
+ * skipped_in_a_row += 1), and the update (returns at once when bad != 0).  No device-to-host copy, no synchronisation: read the
+ * record back (hipMemcpy after a stream synchronise) only where the host syncs anyway -- logging, checkpoints.
+ * Under data parallelism call it after the gradient all-reduce: NaN / Inf survive a sum, the reduced bytes are the same on
+ * every rank, so every rank takes the same decision. */
+typedef struct lbc_adam_state {
+    long long step;              /* number of APPLIED updates (torch.optim.Adam's state["step"]) */
+    long long skipped_total;     /* steps skipped since the record was zeroed */
+    long long skipped_in_a_row;  /* ... since the last applied step */
+    int bad;                     /* decision of the last call: 1 = skipped */
+    int scan_flag;               /* scratch of the scan; zero between calls */
+    float lr_over_bc1;           /* lr / (1 - beta1^step)       of the last applied step */
+    float inv_bc2_sqrt;          /* 1 / sqrt(1 - beta2^step) */
+} lbc_adam_state;
+size_t lbc_adam_state_bytes(void);
+int lbc_adam_step_guarded(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, lbc_adam_state* state_dev, lbc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-operator entry points of the HBM-bound kernels: what the executor above launches between the

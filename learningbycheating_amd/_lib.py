@@ -51,6 +51,12 @@ class AdamChunk(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int), ("pad", c_int)]
 
 
+class AdamState(ctypes.Structure):
+    """lbc_adam_state: the device record of the guarded step (counters are 64-bit)"""
+    _fields_ = [("step", ctypes.c_longlong), ("skipped_total", ctypes.c_longlong), ("skipped_in_a_row", ctypes.c_longlong),
+                ("bad", c_int), ("scan_flag", c_int), ("lr_over_bc1", c_float), ("inv_bc2_sqrt", c_float)]
+
+
 _SIGNATURES = {
     "lbc_last_error": (c_char_p, []),
     "lbc_backend": (c_char_p, []),
@@ -90,6 +96,8 @@ _SIGNATURES = {
     "lbc_loss": (c_int, [c_int, ctypes.POINTER(Camera), c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "lbc_phase2_weight": (c_int, [ctypes.POINTER(Camera), c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "lbc_adam_step": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 5 + [c_int, c_void_p]),
+    "lbc_adam_state_bytes": (c_size_t, []),
+    "lbc_adam_step_guarded": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 5 + [c_void_p, c_void_p]),
     "lbc_bn_stats": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "lbc_bn_finalize_stats": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 5),
     "lbc_bn_apply_relu_add_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),

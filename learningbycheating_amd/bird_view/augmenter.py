@@ -66,11 +66,29 @@ class Recipe:
         return arr, any_blur
 
 
+def rng_state_to_dict(rng):
+    """np.random.RandomState.get_state() as tensors and numbers (what torch.load reads back without unpickling arbitrary objects)"""
+    kind, keys, pos, has_gauss, cached = rng.get_state()
+    assert kind == "MT19937"
+    return {"keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+
+def rng_state_from_dict(rng, sd):
+    rng.set_state(("MT19937", sd["keys"].cpu().numpy().astype(np.uint32), int(sd["pos"]), int(sd["has_gauss"]), float(sd["cached_gaussian"])))
+
+
 class BatchAugmenter:
     def __init__(self, recipe, seed=0):
         self.recipe = recipe
         self.rng = np.random.RandomState(seed)
         self._scratch = None
+
+    def state_dict(self):
+        """the position of the parameter stream (the recipe is a function of the images seen: the loader sets it per batch)"""
+        return {"rng": rng_state_to_dict(self.rng)}
+
+    def load_state_dict(self, sd):
+        rng_state_from_dict(self.rng, sd["rng"])
 
     def augment_batch(self, rgb_u8, params=None):
         """rgb_u8: contiguous uint8 (N,H,W,3) device tensor, augmented in place; returns it"""

@@ -160,6 +160,9 @@ class DeviceLoader:
         self.strategy = augmenter_mod.get(augment)
         self.aug = augmenter_mod.BatchAugmenter(None, seed=seed * 31 + rank) if self.strategy else None
         self.images_seen = dataset.batch_read_number
+        self.position = 0                    # batches handed out by the pass in progress (0 between passes)
+        self.resume_at = 0
+        self._mark = None                    # sampler state before the draws of a batch that is staged but not handed out yet
         cuda = self.device.type == "cuda"
         # Staging in pageable memory unless LBC_PIN_STAGING=1: on the MI355X boxes a pinned buffer that the GPU has read since
         # the CPU last wrote it is slow to rewrite (184 KB: 3.2 ms, then 5.7 ms for the next H2D -- scripts/diag_latency.py),
@@ -190,6 +193,7 @@ class DeviceLoader:
         if self.ready is not None:
             self.ready[k].synchronize()          # the previous H2D out of this staging slot is done
         rgb_np, bv_np = st["rgb"].numpy(), st["bv"].numpy()
+        self._mark = self.rng.get_state()
         draw = getattr(self.data, "sample_index", None)          # command-biased sampling (BiasedBirdViewDataset), else uniform with replacement
         indices = [draw(self.rng) for _ in range(self.batch)] if draw else self.rng.randint(len(self.data), size=self.batch)
         for i, idx in enumerate(indices):
@@ -221,11 +225,20 @@ class DeviceLoader:
         if self.free is not None:
             for e in self.free:
                 e.record()
-        self._fill(0)
-        for i in range(self.samples):
+        start, self.resume_at = self.resume_at, 0     # (a state restored in the middle of a pass: only the rest of that pass)
+        try:
+            yield from self._batches(start)
+        finally:
+            self.position, self._mark = 0, None  # (also when the consumer abandons the pass: the sampler stays where the prefetch left it)
+
+    def _batches(self, start):
+        self._fill(start & 1)
+        for i in range(start, self.samples):
             k = i & 1
             if i + 1 < self.samples:
                 self._fill(k ^ 1)                # stage + enqueue the next batch while this one is consumed
+            else:
+                self._mark = None
             d, st = self.dev[k], self.stage[k]
             if self.ready is not None:
                 torch.cuda.current_stream(self.device).wait_event(self.ready[k])
@@ -251,7 +264,29 @@ class DeviceLoader:
             self.images_seen += n * self.batch_aug
             if self.free is not None:
                 self.free[k].record(torch.cuda.current_stream(self.device))
+            self.position = i + 1
             yield rgb, bv, loc, cmd, speed
+
+    def state_dict(self):
+        """sampler stream, augmenter stream, strength counter and the position inside the pass in progress.  Between passes this is the
+        sampler as it stands (a pass the consumer abandoned has drawn one batch ahead, and the next pass goes on from there, restored
+        or not); inside a pass it is the sampler BEFORE the draws of the batch that is already staged, so that a restored loader draws
+        that batch again and hands out the rest of the pass."""
+        rng = np.random.RandomState()
+        rng.set_state(self._mark if self._mark is not None else self.rng.get_state())
+        return {"images_seen": int(self.images_seen), "position": int(self.position), "frames": len(self.data),
+                "rng": augmenter_mod.rng_state_to_dict(rng), "aug": self.aug.state_dict() if self.aug is not None else None}
+
+    def load_state_dict(self, sd):
+        if int(sd["frames"]) != len(self.data):
+            raise ValueError("DeviceLoader.load_state_dict: the state samples %d frames, this dataset holds %d" % (sd["frames"], len(self.data)))
+        if (sd["aug"] is None) != (self.aug is None):
+            raise ValueError("DeviceLoader.load_state_dict: the state and this loader disagree about augmentation")
+        augmenter_mod.rng_state_from_dict(self.rng, sd["rng"])
+        if self.aug is not None:
+            self.aug.load_state_dict(sd["aug"])
+        self.images_seen = int(sd["images_seen"])
+        self.resume_at = int(sd.get("position", 0))
 
 
 def get_image_device(dataset_dir, batch_size, device, augment=None, n_step=5, gap=5, batch_aug=1, samples=(1000, 10), seed=0, rank=0):

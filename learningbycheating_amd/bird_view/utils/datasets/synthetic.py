@@ -8,10 +8,10 @@ import torch
 
 
 class SyntheticFrames:
-    def __init__(self, n_frames, device, seed=0, rank=0, world=1):
+    def __init__(self, n_frames, device, seed=0, rank=0, world=1, rgb_hw=(160, 384), birdview_hw=(192, 192)):
         g = torch.Generator().manual_seed(seed)
-        self.rgb = torch.randint(0, 256, (n_frames, 160, 384, 3), generator=g, dtype=torch.uint8).to(device)
-        self.birdview = ((torch.rand((n_frames, 192, 192, 7), generator=g) < 0.1).to(torch.uint8) * 255).to(device)
+        self.rgb = torch.randint(0, 256, (n_frames,) + tuple(rgb_hw) + (3,), generator=g, dtype=torch.uint8).to(device)
+        self.birdview = ((torch.rand((n_frames,) + tuple(birdview_hw) + (7,), generator=g) < 0.1).to(torch.uint8) * 255).to(device)
         self.speed = (torch.rand(n_frames, generator=g) * 10).to(device)
         self.command = torch.randint(1, 5, (n_frames,), generator=g).float()
         self.location = (torch.rand((n_frames, 5, 2), generator=g) * 192).to(device)
@@ -23,6 +23,15 @@ class SyntheticFrames:
         idx = torch.randint(0, self.n, (batch_size,), generator=self.gen)
         di = idx.to(self.device)
         return self.rgb[di], self.birdview[di], self.location[di], self.command[idx], self.speed[di]
+
+    def state_dict(self):
+        """the sampler's position (the frames themselves are a function of the constructor's seed)"""
+        return {"n": self.n, "gen": self.gen.get_state().clone()}
+
+    def load_state_dict(self, sd):
+        if int(sd["n"]) != self.n:
+            raise ValueError("SyntheticFrames.load_state_dict: the state samples %d frames, this set holds %d" % (sd["n"], self.n))
+        self.gen.set_state(sd["gen"].cpu())
 
 
 def loader(frames, batch_size, n_batches):

@@ -48,6 +48,7 @@ static long long g_adam_prof_elems = 0;      // lbc_adam_profile_elems: what the
 }  // namespace
 
 extern "C" void lbc_adam_profile_elems(long long n) { g_adam_prof_elems = n > 0 ? n : 0; }
+long long lbc_adam_profile_elems_get() { return g_adam_prof_elems; }     // (adam_guarded.hip books the same table)
 
 int lbc_adam_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int step, hipStream_t s)

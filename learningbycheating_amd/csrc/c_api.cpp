@@ -1,6 +1,7 @@
 // C-ABI entry points (include/lbc_hip.h) over the internal launchers.
 #include "lbc_common.hpp"
 #include "lbc_hip.h"
+#include "lbc_kernels.hpp"
 #include <stddef.h>
 #include <string.h>
 
@@ -15,6 +16,17 @@ const char* lbc_backend(void)
 #endif
 }
 int lbc_version(void) { return LBC_HIP_ABI_VERSION; }
+
+size_t lbc_adam_state_bytes(void) { return sizeof(lbc_adam_state); }
+
+int lbc_adam_step_guarded(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, lbc_adam_state* state_dev, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_adam_chunk) == sizeof(AdamChunk), "chunk layout");
+    static_assert(sizeof(lbc_adam_state) == 40, "lbc_adam_state layout (include/lbc_hip.h)");
+    return lbc_adam_guarded_launch(reinterpret_cast<const AdamChunk*>(chunks_dev), nchunks, lr, beta1, beta2, eps, weight_decay,
+                                   state_dev, (hipStream_t)stream);
+}
 
 // Every entry point that takes a descriptor checks it: struct_size must cover the fields of the first checked layout (ABI 200: everything up to
 // and including split_workspace_bytes) and must not exceed this library's struct.  A host built against an OLDER header of the same major

@@ -257,3 +257,9 @@ int lbc_phase2_weight_launch(const LossArgs& a, hipStream_t s);   // DAgger resa
 struct AdamChunk { float* p; const float* g; float* m; float* v; int n; int pad; };
 int lbc_adam_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int step, hipStream_t s);
+long long lbc_adam_profile_elems_get();      // what lbc_adam_profile_elems() was last given
+// adam_guarded.hip: non-finite scan of the gradients -> bookkeeping on the device record -> the same update, skipped as a whole when
+// the scan found something.  No device-to-host traffic; the step count lives in *state_dev (include/lbc_hip.h lbc_adam_state).
+struct lbc_adam_state;
+int lbc_adam_guarded_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, lbc_adam_state* state_dev, hipStream_t s);

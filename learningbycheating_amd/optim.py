@@ -12,11 +12,21 @@ CHUNK = 32768
 
 class FusedAdam:
     """Adam over (param, grad) pairs whose physical memory is dense (any stride permutation);
-    grads are the engine's flat-buffer views, so p, g, m, v share one element order."""
+    grads are the engine's flat-buffer views, so p, g, m, v share one element order.
 
-    def __init__(self, named_params, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    guarded=True: every step first scans the gradients for NaN / +-Inf on the device (csrc/adam_guarded.hip) and skips the whole
+    update when it finds one -- parameters, both moments and the step count keep their bits.  The step count then lives in a device
+    record (lbc_adam_state), no step ever syncs; `step_count` and `skipped()` read the record back (a device-to-host copy: for logging
+    and checkpoints only).
+
+    state_dict() / load_state_dict() speak torch.optim.Adam's own format (moments in the parameters' logical shapes, parameters indexed
+    in named_parameters() order), so a sidecar written here loads into a torch.optim.Adam over the reference-layout module and back."""
+
+    def __init__(self, named_params, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, guarded=False):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.step_count = 0
+        self.guarded = bool(guarded)
+        self._step_count = 0
+        self.all_names = [n for n, _ in named_params]
         self.names = [n for n, _ in named_params if n in grads]
         params = dict(named_params)
         # moments in the gradients' element order, every tensor starting on a 64-element (256-byte) boundary: adam_k moves
@@ -47,12 +57,117 @@ class FusedAdam:
         _lib.get().lbc_adam_profile_elems(sum(params[n].numel() for n in self.names))     # (books the launch profiler's 28 bytes per element)
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
         self._keep = (params, grads)
+        self.record = None
+        if self.guarded:
+            nbytes = int(_lib.get().lbc_adam_state_bytes())
+            assert nbytes == ctypes.sizeof(_lib.AdamState), "lbc_adam_state layout"
+            self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)       # (torch allocations are 256-byte aligned)
 
+    # ---- the step ---------------------------------------------------------------------------
     def step(self):
-        self.step_count += 1
+        if self.guarded:
+            _lib.check(_lib.get().lbc_adam_step_guarded(_lib.ptr(self.table), self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                        self.weight_decay, _lib.ptr(self.record), _lib.stream_for(self.table)), "adam_step_guarded")
+            return
+        self._step_count += 1
         _lib.check(_lib.get().lbc_adam_step(_lib.ptr(self.table), self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
-                                            self.weight_decay, self.step_count, _lib.stream_for(self.table)), "adam_step")
+                                            self.weight_decay, self._step_count, _lib.stream_for(self.table)), "adam_step")
+
+    def _read_record(self):
+        return _lib.AdamState.from_buffer_copy(self.record.cpu().numpy().tobytes())       # (the copy waits for the steps in flight)
+
+    def _write_record(self, step, skipped_total=0, skipped_in_a_row=0):
+        # the coefficients stay zero: the bookkeeping kernel derives them from `step` before the next applied update reads them
+        rec = _lib.AdamState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0)
+        self.record.copy_(torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8))
+
+    @property
+    def step_count(self):
+        """number of applied updates (guarded: read from the device record -- a sync)"""
+        return int(self._read_record().step) if self.guarded else self._step_count
+
+    @step_count.setter
+    def step_count(self, value):
+        if self.guarded:
+            r = self._read_record()
+            self._write_record(value, r.skipped_total, r.skipped_in_a_row)
+        else:
+            self._step_count = int(value)
+
+    def skipped(self):
+        """(steps skipped in total, steps skipped since the last applied one); (0, 0) without the guard.  A sync when guarded."""
+        if not self.guarded:
+            return (0, 0)
+        r = self._read_record()
+        return (int(r.skipped_total), int(r.skipped_in_a_row))
+
+    def set_skipped(self, total, in_a_row):
+        if self.guarded:
+            self._write_record(self._read_record().step, total, in_a_row)
 
     def state_of(self, name):
         off, n = self.offsets[name]
         return self.exp_avg[off:off + n], self.exp_avg_sq[off:off + n]
+
+    # ---- torch.optim.Adam's state_dict format ------------------------------------------------
+    def _logical(self, name):
+        """the two moments of `name` as views in the parameter's logical shape (the flat buffers are in its physical order)"""
+        p = self._keep[0][name].data
+        m, v = self.state_of(name)
+        return torch.as_strided(m, p.shape, p.stride()), torch.as_strided(v, p.shape, p.stride())
+
+    def state_dict(self):
+        """{"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]} as torch.optim.Adam.state_dict() writes it: i counts
+        named_parameters(); a parameter that is never stepped (conv.fc.* has no gradient) has no entry, and before the first applied
+        step nobody has one -- exactly what torch keeps for never-stepped parameters.  Tensors are CPU copies."""
+        step = self.step_count
+        state = {}
+        if step > 0:
+            for i, n in enumerate(self.all_names):
+                if n in self.offsets:
+                    m, v = self._logical(n)
+                    state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m.cpu().clone(), "exp_avg_sq": v.cpu().clone()}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": False, "params": list(range(len(self.all_names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """takes what state_dict() or a torch.optim.Adam over the same parameters (in named_parameters() order) wrote; the guard counters
+        are not part of torch's format and are left alone (NativeTrainer.state_dict carries them)"""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or list(groups[0]["params"]) != list(range(len(self.all_names))):
+            raise ValueError("FusedAdam.load_state_dict: expected one parameter group over %d parameters in named_parameters() order, got %s"
+                             % (len(self.all_names), [len(g["params"]) for g in groups]))
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("decoupled_weight_decay"):
+            raise ValueError("FusedAdam.load_state_dict: amsgrad / maximize / decoupled weight decay are not implemented")
+        state = sd["state"]
+        steps = set()
+        for i, n in enumerate(self.all_names):
+            st = state.get(i)
+            if n not in self.offsets:
+                if st:
+                    raise ValueError("FusedAdam.load_state_dict: %s carries optimizer state, but has no gradient here" % n)
+                continue
+            if not st:
+                steps.add(0)
+                continue
+            p = self._keep[0][n]
+            if tuple(st["exp_avg"].shape) != tuple(p.shape) or tuple(st["exp_avg_sq"].shape) != tuple(p.shape):
+                raise ValueError("FusedAdam.load_state_dict: moments of %s have shape %s, the parameter %s"
+                                 % (n, tuple(st["exp_avg"].shape), tuple(p.shape)))
+            steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise ValueError("FusedAdam.load_state_dict: the parameters carry different step counts %s; this optimizer keeps one" % sorted(steps))
+        step = steps.pop() if steps else 0
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        if step > 0:
+            for i, n in enumerate(self.all_names):
+                if n in self.offsets:
+                    m, v = self._logical(n)
+                    m.copy_(state[i]["exp_avg"])            # (copy_ maps logical indices: any memory format on the other side)
+                    v.copy_(state[i]["exp_avg_sq"])
+        self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
+        self.step_count = step

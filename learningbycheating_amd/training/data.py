@@ -14,20 +14,44 @@ class _SyntheticLoader:
         self.strategy = augmenter_mod.get(augment)
         self.aug = augmenter_mod.BatchAugmenter(None, seed=seed) if self.strategy else None
         self.images_seen = 819200            # the reference's ImageDataset starts its strength counter here (image_lmdb.py:72)
+        self.position = 0                    # batches handed out by the pass in progress (0 between passes)
+        self.resume_at = 0
 
     def __len__(self):
         return self.n_batches
 
     def __iter__(self):
-        for _ in range(self.n_batches):
-            rgb, bv, loc, cmd, speed = self.frames.batch(self.batch)
-            if self.batch_aug > 1:           # reference train_image_phase1.py:131-154,183-189
-                rgb, bv, loc, cmd, speed = (t.repeat_interleave(self.batch_aug, dim=0) for t in (rgb, bv, loc, cmd, speed))
-            if self.strategy is not None:
-                self.aug.recipe = self.strategy(self.images_seen)
-                self.aug.augment_batch(rgb)  # (rgb is a gathered copy of the resident frames)
-            self.images_seen += rgb.shape[0]
-            yield rgb, bv, loc, cmd, speed
+        start, self.resume_at = self.resume_at, 0     # (a state restored in the middle of a pass: only the rest of that pass)
+        try:
+            for i in range(start, self.n_batches):
+                rgb, bv, loc, cmd, speed = self.frames.batch(self.batch)
+                if self.batch_aug > 1:           # reference train_image_phase1.py:131-154,183-189
+                    rgb, bv, loc, cmd, speed = (t.repeat_interleave(self.batch_aug, dim=0) for t in (rgb, bv, loc, cmd, speed))
+                if self.strategy is not None:
+                    self.aug.recipe = self.strategy(self.images_seen)
+                    self.aug.augment_batch(rgb)  # (rgb is a gathered copy of the resident frames)
+                self.images_seen += rgb.shape[0]
+                self.position = i + 1
+                yield rgb, bv, loc, cmd, speed
+        finally:
+            self.position = 0                    # (also when the consumer abandons the pass: the reference's 11-batch dry run)
+
+    def state_dict(self):
+        """everything the next batch depends on: the frame sampler's generator, the augmenter's parameter stream and the image counter
+        that sets the augmentation strength, and the position inside the pass in progress.  Exact at any batch boundary (nothing is
+        prefetched): a loader restored in the middle of a pass hands out the rest of that pass, then whole passes again."""
+        return {"images_seen": int(self.images_seen), "position": int(self.position), "frames": self.frames.state_dict(),
+                "aug": self.aug.state_dict() if self.aug is not None else None}
+
+    def load_state_dict(self, sd):
+        if (sd["aug"] is None) != (self.aug is None):
+            raise ValueError("_SyntheticLoader.load_state_dict: the state was saved %s augmentation, this loader runs %s"
+                             % (("without", "with") if sd["aug"] is None else ("with", "without")))
+        self.images_seen = int(sd["images_seen"])
+        self.resume_at = int(sd.get("position", 0))
+        self.frames.load_state_dict(sd["frames"])
+        if self.aug is not None:
+            self.aug.load_state_dict(sd["aug"])
 
 
 def make_loaders(config, device, rank=0, world=1):

@@ -24,10 +24,20 @@ def camera_struct(**kw):
 class NativeTrainer:
     """phase: 1 (student vs teacher, all branches, map space), 0 (student vs teacher, selected branch,
     image space), 'birdview' (privileged agent vs ground-truth waypoints), 'l1_all' (all branches vs
-    given normalised targets; used to warm-start synthetic benchmarks below the horizon)."""
+    given normalised targets; used to warm-start synthetic benchmarks below the horizon).
+
+    skip_nonfinite=True: the optimizer scans the (all-reduced) gradients on the device and skips the update of a step that holds a NaN
+    or an infinity -- the phase-1 / phase-2 loss has a 1 / y pole on the horizon row -- without a host round trip.  What a skipped step
+    leaves behind: parameters, both Adam moments and Adam's step count bit-identical to before the step; the BatchNorm running
+    statistics and counters HAVE advanced, because the forward wrote them before the loss existed (what a `continue` after the forward
+    would do in the reference loop).  The scan sits behind StageAllReducer.wait(): non-finite values survive the sum and the bf16
+    wire, every rank reads the same reduced bytes, so every rank takes the same decision with no extra collective.
+    `skipped()` -> (total, in a row) reads the device counters (a sync: call it where the loop syncs anyway).
+
+    state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
-                 sync_bn=False, teacher_shape=(7, 192, 192)):
+                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False):
         self.student, self.teacher, self.phase, self.batch, self.world = student, teacher, phase, batch, world_size
         self.device = device
         student.train()
@@ -41,7 +51,8 @@ class NativeTrainer:
             self.teng.set_frozen(True)
             self._teacher_versions = self._versions(teacher)
         self.cam = camera or camera_struct()
-        self.opt = FusedAdam(list(student.named_parameters()), self.eng.grad_views, lr=lr)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.opt = FusedAdam(list(student.named_parameters()), self.eng.grad_views, lr=lr, guarded=self.skip_nonfinite)
         self.reducer = StageAllReducer(self.eng.grad_flat, self.eng.grad_spans, group, grad_dtype=grad_dtype)   # grad_dtype: see parallel.py
         self.sync_bn = bool(sync_bn and world_size > 1)
         if sync_bn and world_size > 1:
@@ -130,3 +141,48 @@ class NativeTrainer:
             self.reducer.wait()
             self.opt.step()
         return self.loss[:n]
+
+    # ---- resumable state ---------------------------------------------------------------------
+    def skipped(self):
+        return self.opt.skipped()
+
+    def _layout(self):
+        return [[n, list(p.shape)] for n, p in self.student.named_parameters()]
+
+    def state_dict(self):
+        """student state_dict (parameters + BatchNorm buffers, CPU copies), the optimizer in torch.optim.Adam's format, the guard's
+        counters, and what the state was produced under (phase, parameter layout, precision, world size).  The frozen teacher is not
+        part of it: the scripts load it from its own checkpoint.  Syncs the device."""
+        total, row = self.opt.skipped()
+        return {"format": 1, "phase": self.phase, "precision": getattr(self.student, "precision", "fp32"), "world_size": int(self.world),
+                "layout": self._layout(),
+                "student": {k: v.detach().cpu().clone() for k, v in self.student.state_dict().items()},
+                "optimizer": self.opt.state_dict(),
+                "guard": {"enabled": self.skip_nonfinite, "skipped_total": total, "skipped_in_a_row": row}}
+
+    def load_state_dict(self, sd):
+        """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size or precision
+        and says so (returned notes, also logged).  The guard setting need not match: counters are restored where this trainer has
+        them.  Parameters and buffers are written in place, and the engine derives its weight copies (bf16 / split planes, folded
+        BatchNorm) again."""
+        import logging
+        if sd.get("format") != 1:
+            raise ValueError("NativeTrainer.load_state_dict: unknown state format %r" % (sd.get("format"),))
+        if sd["phase"] != self.phase:
+            raise ValueError("NativeTrainer.load_state_dict: the state was saved in phase %r, this trainer runs phase %r" % (sd["phase"], self.phase))
+        if [[n, list(s)] for n, s in sd["layout"]] != self._layout():
+            raise ValueError("NativeTrainer.load_state_dict: the state was saved for another parameter layout (%d tensors, this model has %d "
+                             "or other names / shapes)" % (len(sd["layout"]), len(self._layout())))
+        notes = []
+        if int(sd["world_size"]) != int(self.world):
+            notes.append("state saved under world size %d, continuing under %d" % (sd["world_size"], self.world))
+        if sd["precision"] != getattr(self.student, "precision", "fp32"):
+            notes.append("state saved in precision %s, continuing in %s" % (sd["precision"], getattr(self.student, "precision", "fp32")))
+        for n in notes:
+            logging.getLogger(__name__).warning("NativeTrainer.load_state_dict: %s", n)
+        self.student.load_state_dict(sd["student"])
+        self.opt.load_state_dict(sd["optimizer"])
+        g = sd.get("guard") or {}
+        self.opt.set_skipped(g.get("skipped_total", 0), g.get("skipped_in_a_row", 0))
+        self.eng.invalidate()
+        return notes

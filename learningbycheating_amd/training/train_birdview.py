@@ -14,6 +14,7 @@ from ..bird_view.utils import bz_utils as bzu
 from .data import make_loaders
 from ..bird_view.utils.train_utils import one_hot
 from ..parallel import broadcast_module
+from . import resume
 from .native import NativeTrainer
 
 BACKBONE = "resnet18"
@@ -22,17 +23,22 @@ N_STEP = 5
 SAVE_EPOCHS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1000]
 
 
-def train_or_eval(trainer, data, is_train, config, is_first_epoch):
+def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
     """reference train_birdview.py:102-153"""
     tick = time.time()
-    for i, (rgb_image, birdview, location, command, speed) in enumerate(data):
+    for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
         loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=is_train and not is_first_epoch, train_mode=is_train)
         if (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
+            skipped = resume.check_skipped(config, trainer, "train_birdview") if is_train else None
+            if skipped is not None:
+                bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
+        if is_train and not is_first_epoch and loaders is not None:
+            resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
 
@@ -43,7 +49,8 @@ def train(config):
     bzu.log.save_config({k: v for k, v in config.items() if k not in ("rank", "world_size")})
     net = BirdViewPolicyModelSS(config["model_args"]["backbone"]).to(device)
     net.precision = config.get("precision", "fp32")
-    if config["resume"]:
+    full_state = config["resume"] and (Path(config["log_dir"]) / resume.STATE_NAME).exists()
+    if config["resume"] and not full_state:
         # the reference takes glob('model-*.th')[-1] unsorted (train_birdview.py:164-169); sort numerically instead
         ckpts = sorted(Path(config["log_dir"]).glob("model-*.th"), key=lambda p: int(p.stem.split("-")[1]))
         if ckpts:
@@ -51,10 +58,15 @@ def train(config):
     broadcast_module(net)
     bs = config["data_args"]["batch_size"]
     data_train, data_val = make_loaders(config, device, rank, world)
-    trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world)
-    for epoch in range(int(config["max_epoch"]) + 1):
+    trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world,
+                            skip_nonfinite=config.get("skip_nonfinite", False))
+    loaders = {"train": data_train, "val": data_val}
+    # --resume: the full state (train_state.th: optimizer, loaders, RNG, epoch) when there is one; without it, as before, the newest
+    # model-%d.th with a fresh Adam from epoch 0
+    state = resume.load(config, trainer, loaders) if full_state else None
+    for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):
         net.train()
-        train_or_eval(trainer, data_train, True, config, epoch == 0)
+        train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
         net.eval()                              # reference train_birdview.py:175-176: validation pass after every epoch
         train_or_eval(trainer, data_val, False, config, epoch == 0)
         net.train()
@@ -63,6 +75,7 @@ def train(config):
         rec = bzu.log.end_epoch()
         if rank == 0:
             print(rec)
+        resume.save(config, trainer, loaders, epoch)
     return net
 
 
@@ -86,6 +99,7 @@ def main(argv=None):
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
                         help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
                              "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
+    resume.add_arguments(parser, with_resume=False)
     parsed = parser.parse_args(argv)
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
@@ -102,6 +116,7 @@ def main(argv=None):
         "model_args": {"model": "birdview_dian", "input_channel": 7, "backbone": BACKBONE},
         "synthetic": parsed.synthetic, "iters_per_epoch": parsed.iters_per_epoch, "rank": rank, "world_size": world,
     }
+    config.update(resume.config_entries(parsed))
     train(config)
     if world > 1:
         dist.destroy_process_group()

@@ -18,6 +18,7 @@ from ..bird_view.utils import bz_utils as bzu
 from .data import make_loaders
 from ..bird_view.utils.train_utils import one_hot
 from ..parallel import broadcast_module
+from . import resume
 from .native import NativeTrainer, camera_struct
 
 BACKBONE = "resnet34"
@@ -28,17 +29,22 @@ CROP_SIZE = 192
 SAVE_EPOCHS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1000]
 
 
-def train_or_eval(trainer, data, is_train, config, is_first_epoch):
+def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
     """reference train_image_phase0.py:152-209"""
     tick = time.time()
-    for i, (rgb_image, birdview, location, command, speed) in enumerate(data):
+    for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
         loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=is_train and not is_first_epoch, train_mode=is_train)
         if (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
+            skipped = resume.check_skipped(config, trainer, "phase 0") if is_train else None
+            if skipped is not None:
+                bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
+        if is_train and not is_first_epoch and loaders is not None:
+            resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
 
@@ -61,10 +67,13 @@ def train(config):
     bs = config["data_args"]["batch_size"]
     data_train, data_val = make_loaders(config, device, rank, world)
     cam = camera_struct(**{k: float(v) for k, v in config["camera_args"].items()})
-    trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam)
-    for epoch in range(int(config["max_epoch"]) + 1):
+    trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
+                            skip_nonfinite=config.get("skip_nonfinite", False))
+    loaders = {"train": data_train, "val": data_val}
+    state = resume.load(config, trainer, loaders)
+    for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):
         net.train()
-        train_or_eval(trainer, data_train, True, config, epoch == 0)
+        train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
         net.eval()                              # reference train_image_phase0.py:236-237: validation pass after every epoch
         train_or_eval(trainer, data_val, False, config, epoch == 0)
         net.train()
@@ -73,6 +82,7 @@ def train(config):
         rec = bzu.log.end_epoch()
         if rank == 0:
             print(rec)
+        resume.save(config, trainer, loaders, epoch)
     return net
 
 
@@ -93,6 +103,7 @@ def main(argv=None):
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
                         help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
                              "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
+    resume.add_arguments(parser)
     parsed = parser.parse_args(argv)
     if parsed.pretrained:
         raise SystemExit("--pretrained downloads ImageNet weights (reference resnet.py:175-178); no network here")
@@ -112,6 +123,7 @@ def main(argv=None):
         "teacher_args": {"model_path": parsed.teacher_path},
         "synthetic": parsed.synthetic, "iters_per_epoch": parsed.iters_per_epoch, "rank": rank, "world_size": world,
     }
+    config.update(resume.config_entries(parsed))
     train(config)
     if world > 1:
         dist.destroy_process_group()

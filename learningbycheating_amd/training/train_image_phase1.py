@@ -3,7 +3,8 @@
 Same flags, config.json schema and model-%d.th naming as the reference; the loop body runs on the native executor
 (NativeTrainer.step = teacher forward, student forward, unprojection + L1 over the four branches, backward, RCCL
 gradient all-reduce, fused Adam).  New flags: --synthetic N (device-resident synthetic frames instead of the LMDB
-dataset), --iters_per_epoch, and one-process-per-GPU launch through torch.distributed.run.
+dataset), --iters_per_epoch, one-process-per-GPU launch through torch.distributed.run, and --save_state / --resume /
+--skip-nonfinite (training/resume.py: a run that can be stopped and continued bit for bit, and that survives a step on the loss's pole).
 
 CoordConverter / LocationLoss keep the reference's call signatures (train_image_phase1.py:35-70) for callers that
 want the map-space waypoints; they are thin torch expressions over (N,4,5,2) tensors, the timed path uses the fused
@@ -23,6 +24,7 @@ from ..bird_view.utils import bz_utils as bzu
 from .data import make_loaders
 from ..bird_view.utils.train_utils import one_hot
 from ..parallel import broadcast_module
+from . import resume
 from .native import NativeTrainer, camera_struct
 
 BACKBONE = "resnet34"
@@ -55,11 +57,12 @@ class LocationLoss(torch.nn.Module):
         return torch.mean(torch.abs(pred_locations - teac_locations), dim=(1, 2, 3))
 
 
-def train_or_eval(trainer, data, is_train, config, is_first_epoch):
+def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
     """reference train_image_phase1.py:157-229; epoch 0 is the reference's 11-iteration dry run without updates"""
     tick = time.time()
     device = config["device"]
-    for i, (rgb_image, birdview, location, command, speed) in enumerate(data):
+    # (a loader restored in the middle of its pass hands out the rest of it: the iteration count goes on where it stood)
+    for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(device)
         if is_train and config["speed_noise"] > 0:
             speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
@@ -67,13 +70,18 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch):
         should_log = (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch
         if should_log:
             lm = loss.mean().item()          # device->host sync only when logging, as the reference (:207-221)
-            if not np.isfinite(lm):
+            skipped = resume.check_skipped(config, trainer, "phase 1") if is_train else None
+            if skipped is not None:
+                bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
+            if not np.isfinite(lm) and not config.get("skip_nonfinite"):
                 raise FloatingPointError("phase-1 loss is %s: a predicted waypoint reached the horizon (1/y pole of the "
                                          "unprojection); start from a phase-0 checkpoint" % lm)
             bzu.log.scalar(is_train=is_train, loss_mean=lm)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9), images_per_sec=rgb_image.shape[0] * config["world_size"] / max(now - tick, 1e-9))
         tick = now
+        if is_train and not is_first_epoch and loaders is not None:
+            resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
 
@@ -100,10 +108,12 @@ def train(config):
     data_train, data_val = make_loaders(config, device, rank, world)
     cam = camera_struct(**{k: float(v) for k, v in config["agent_args"]["camera_args"].items()})
     trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=1, lr=config["optimizer_args"]["lr"],
-                            world_size=world, camera=cam)
-    for epoch in range(int(config["max_epoch"]) + 1):
+                            world_size=world, camera=cam, skip_nonfinite=config.get("skip_nonfinite", False))
+    loaders = {"train": data_train, "val": data_val}
+    state = resume.load(config, trainer, loaders)
+    for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):
         net.train()
-        train_or_eval(trainer, data_train, True, config, epoch == 0)
+        train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
         net.eval()                              # reference train_image_phase1.py:255-256: a validation pass after every epoch
         train_or_eval(trainer, data_val, False, config, epoch == 0)
         net.train()
@@ -112,6 +122,7 @@ def train(config):
         rec = bzu.log.end_epoch()
         if rank == 0:
             print(rec)
+        resume.save(config, trainer, loaders, epoch)
     return net
 
 
@@ -135,6 +146,7 @@ def main(argv=None):
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
                         help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
                              "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
+    resume.add_arguments(parser)
     parsed = parser.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -155,6 +167,7 @@ def main(argv=None):
         "agent_args": {"camera_args": {"w": 384, "h": 160, "fov": 90, "world_y": 1.4, "fixed_offset": 4.0}},
         "synthetic": parsed.synthetic, "iters_per_epoch": parsed.iters_per_epoch, "rank": rank, "world_size": world,
     }
+    config.update(resume.config_entries(parsed))
     train(config)
     if world > 1:
         dist.destroy_process_group()

@@ -41,7 +41,8 @@ def _train(replay_buffer, trainer, config, episode):
     bs = config["batch_size"]
     net, teacher_net = trainer.student, trainer.teacher
     for epoch in range(config["epoch_per_episode"]):
-        trainer.opt = FusedAdam(list(net.named_parameters()), trainer.eng.grad_views, lr=1e-4)   # fresh moments each epoch
+        trainer.opt = FusedAdam(list(net.named_parameters()), trainer.eng.grad_views, lr=1e-4,
+                                guarded=config.get("skip_nonfinite", False))                     # fresh moments each epoch
         net.train()
         replay_buffer.init_new_weights()
         for i in range(len(replay_buffer) // bs):                                              # drop_last=True
@@ -54,6 +55,12 @@ def _train(replay_buffer, trainer, config, episode):
             replay_buffer.update_weights(idx, phase2_weights(trainer, trainer.last_pred[0], trainer.last_teacher[0]))
             if i % int(config["log_iterations"]) == 0:
                 bzu.log.scalar(loss_mean=loss.mean().item())
+                if config.get("skip_nonfinite"):
+                    total, row = trainer.skipped()
+                    bzu.log.scalar(skipped_steps=total)
+                    if row > config["max_skipped"]:
+                        raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
+                                                 % (row, config["max_skipped"]))
         replay_buffer.normalize_weights()
         # the reference evaluates (eval mode) and visualises the 32 highest-weight samples here (:229-250); visualisation
         # is outside the hot path, the forward is kept so that the same kernels run
@@ -94,6 +101,9 @@ def main(argv=None):
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
                         help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
                              "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
+    parser.add_argument("--skip-nonfinite", action="store_true",
+                        help="skip (on the device) every optimizer step whose gradients hold a NaN or an infinity")
+    parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
     parsed = parser.parse_args(argv)
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
@@ -107,6 +117,8 @@ def main(argv=None):
               "precision": parsed.precision,
               "model_args": {"model": "image_ss", "backbone": BACKBONE},
               "agent_args": {"camera_args": {"w": 384, "h": 160, "fov": 90, "world_y": 1.4, "fixed_offset": 4.0}}}
+    if parsed.skip_nonfinite:
+        config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
     bzu.log.init(parsed.log_dir, rank)
     bzu.log.save_config({k: v for k, v in config.items() if k != "rank"})
     net = ImagePolicyModelSS(BACKBONE, all_branch=True).to(device)
@@ -119,7 +131,7 @@ def main(argv=None):
     broadcast_module(net)
     broadcast_module(teacher)
     trainer = NativeTrainer(net, teacher, parsed.batch_size, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
-                            camera=camera_struct())
+                            camera=camera_struct(), skip_nonfinite=bool(parsed.skip_nonfinite))
     buf = synthetic_buffer(parsed.synthetic // world, device, seed=rank)
     for episode in range(int(parsed.max_episode)):
         t0 = time.time()
