@@ -358,6 +358,33 @@ int lbc_birdview_warp_crop_u8(const unsigned char* src, unsigned char* dst, cons
 int lbc_augment_rgb_u8(unsigned char* images, const lbc_aug_params* params_dev, float* scratch, int N, int H, int W, int any_blur,
                        lbc_stream_t stream);
 
+/* Device-resident prioritised replay buffer of phase 2 (reference training/phase2_utils.py:190-289): weighted sampling, frame gather
+ * with the --batch_aug fan-out, and the write-back of the new weights, without a host round trip.  Every call only enqueues on
+ * `stream`; none copies to the host or synchronises.  Indices are trusted where no bound is passed (gather, scatter, meta): they come
+ * from lbc_replay_sample or from a permutation of the buffer.
+ * lbc_replay_cdf: cdf[i] = w[0] + ... + w[i] in double (inclusive), n >= 1.  A weight that is negative, NaN or +-Inf contributes 0 and
+ *   is counted in *bad_count (device memory, overwritten).  Deterministic (fixed summation order, no atomics); three launches.
+ * lbc_replay_sample: B draws with replacement, probability w[i] / sum(w).  Draw j of step t is counter-based (no device state):
+ *   h1 = hash3(seed ^ t_hi, 2j, t_lo), h2 = hash3(seed ^ t_hi, 2j + 1, t_lo) with t_lo / t_hi the 32-bit halves of `step` and
+ *   hash3(s, a, b) = H(s ^ H(a * 0x9E3779B9 + H(b + 0x85EBCA6B))), H = the "lowbias32" finaliser (x ^= x >> 16; x *= 0x7feb352d;
+ *   x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16);  u = ((h1 >> 5) * 2^26 + (h2 >> 6)) * 2^-53 * cdf[n-1];  idx[j] = the first i with
+ *   cdf[i] > u.  An entry of weight 0 is never returned (exactly so where the prefix sums are exact; with arbitrary weights two
+ *   neighbouring sums may differ by one unit in the last place of a double, which can give a zero weight a share of 2^-53 of the
+ *   total); should the product round up to cdf[n-1], the last entry of non-zero weight is.  cdf[n-1] must be > 0 (the caller checks the total it reads back once per epoch).
+ * lbc_replay_gather_u8: dst row b * reps + k = src row idx[b], k < reps (torch.repeat_interleave of the gathered rows).  row_bytes
+ *   must be a multiple of 16 and both base pointers 16-byte aligned (LBC_EINVAL otherwise): rows move as 16-byte words.
+ * lbc_replay_scatter_u8: dst row slot[m] = src row m, m < M (fills free slots, overwrites evicted ones); slots must be distinct.
+ * lbc_replay_meta: speed_out[b * reps + k] = speed[idx[b]]; onehot_out[b * reps + k][0..3] = one-hot of clamp(cmd[idx[b]] - 1, 0, 3)
+ *   (the rule of bird_view/utils/train_utils.py one_hot: commands are 1..4, anything below selects branch 0, anything above branch 3).
+ * lbc_replay_writeback: new_w[idx[b]] = (w_batch[b * reps] + ... + w_batch[b * reps + reps - 1]) / reps, summed in f32 in index order.
+ *   Where several b carry the same index the LAST one wins (numpy fancy assignment); idx[b] < 0 or >= n is ignored.  B <= 1024. */
+int lbc_replay_cdf(const float* w, int n, double* cdf, long long* bad_count, lbc_stream_t stream);
+int lbc_replay_sample(const double* cdf, int n, unsigned seed, unsigned long long step, int B, int* idx, lbc_stream_t stream);
+int lbc_replay_gather_u8(const unsigned char* src, long long row_bytes, const int* idx, int B, int reps, unsigned char* dst, lbc_stream_t stream);
+int lbc_replay_scatter_u8(const unsigned char* src, long long row_bytes, const int* slot, int M, unsigned char* dst, lbc_stream_t stream);
+int lbc_replay_meta(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, lbc_stream_t stream);
+int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, lbc_stream_t stream);
+
 /* Runtime options (A/B switches, tuning knobs, test hooks): names are the LBC_* environment variables that initialise the
  * table at load time; -1 = unset.  The one option read when a network is created (LBC_NO_SIDE_STREAM) applies to
  * networks created afterwards.  An LBC_* environment variable that is not in the table (a switch of an earlier round, a typo) is reported

@@ -269,4 +269,35 @@ int lbc_augment_rgb_u8(unsigned char* images, const lbc_aug_params* params_dev, 
     return lbc_augment_u8(images, reinterpret_cast<const AugParams*>(params_dev), scratch, N, H, W, any_blur, (hipStream_t)stream);
 }
 
+// ---- device-resident replay buffer (phase 2) ------------------------------------------------------------------
+int lbc_replay_cdf(const float* w, int n, double* cdf, long long* bad_count, lbc_stream_t stream)
+{
+    return lbc_replay_cdf_launch(w, n, cdf, bad_count, (hipStream_t)stream);
+}
+
+int lbc_replay_sample(const double* cdf, int n, unsigned seed, unsigned long long step, int B, int* idx, lbc_stream_t stream)
+{
+    return lbc_replay_sample_launch(cdf, n, seed, step, B, idx, (hipStream_t)stream);
+}
+
+int lbc_replay_gather_u8(const unsigned char* src, long long row_bytes, const int* idx, int B, int reps, unsigned char* dst, lbc_stream_t stream)
+{
+    return lbc_replay_gather_launch(src, row_bytes, idx, B, reps, dst, (hipStream_t)stream);
+}
+
+int lbc_replay_scatter_u8(const unsigned char* src, long long row_bytes, const int* slot, int M, unsigned char* dst, lbc_stream_t stream)
+{
+    return lbc_replay_scatter_launch(src, row_bytes, slot, M, dst, (hipStream_t)stream);
+}
+
+int lbc_replay_meta(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, lbc_stream_t stream)
+{
+    return lbc_replay_meta_launch(speed, cmd, idx, B, reps, speed_out, onehot_out, (hipStream_t)stream);
+}
+
+int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, lbc_stream_t stream)
+{
+    return lbc_replay_writeback_launch(w_batch, idx, B, reps, n, new_w, (hipStream_t)stream);
+}
+
 }  // extern "C"

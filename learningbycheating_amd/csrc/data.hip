@@ -11,17 +11,11 @@
 // (image seed, operator, pixel | cell, channel), so results are reproducible and testable against a numpy restatement.
 // Between operators a pixel is a uint8: every operator rounds to nearest and clips to [0, 255] like imgaug's uint8 paths.
 #include "lbc_common.hpp"
+#include "lbc_hash.hpp"
 #include "lbc_kernels.hpp"
 
 namespace {
 
-__device__ __forceinline__ unsigned hash_u32(unsigned x)
-{
-    // "lowbias32" integer finaliser (public domain, Chris Wellons): full avalanche in 2 multiplies
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ unsigned hash3(unsigned seed, unsigned a, unsigned b) { return hash_u32(seed ^ hash_u32(a * 0x9E3779B9U + hash_u32(b + 0x85EBCA6BU))); }
 __device__ __forceinline__ float u01(unsigned h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float clip_u8(float v) { return fminf(fmaxf(rintf(v), 0.f), 255.f); }
 

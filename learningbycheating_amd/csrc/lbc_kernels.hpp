@@ -237,6 +237,14 @@ struct AugParams {               // one per image; layout = lbc_aug_params of in
 int lbc_crop_u8(const unsigned char* src, unsigned char* dst, int N, int SH, int SW, int C, int y0, int x0, int H, int W, hipStream_t s);
 int lbc_augment_u8(unsigned char* img, const AugParams* params_dev, float* tmp, int N, int H, int W, int any_blur, hipStream_t s);
 
+// ---- device-resident replay buffer of phase 2 (replay.hip) ------------------------------------------------
+int lbc_replay_cdf_launch(const float* w, int n, double* cdf, long long* bad_count, hipStream_t s);
+int lbc_replay_sample_launch(const double* cdf, int n, unsigned seed, unsigned long long step, int B, int* idx, hipStream_t s);
+int lbc_replay_gather_launch(const unsigned char* src, long long row_bytes, const int* idx, int B, int reps, unsigned char* dst, hipStream_t s);
+int lbc_replay_scatter_launch(const unsigned char* src, long long row_bytes, const int* slot, int M, unsigned char* dst, hipStream_t s);
+int lbc_replay_meta_launch(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, hipStream_t s);
+int lbc_replay_writeback_launch(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, hipStream_t s);
+
 // ---- losses (phase 0 / phase 1 / bird-view) -------------------------------------------
 struct LossArgs {
     const float* pred;           // student output, normalised [-1,1]

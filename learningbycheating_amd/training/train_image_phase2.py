@@ -4,7 +4,14 @@
 `rollout` (train_image_phase2.py:61-149) drives a live CARLA server and is outside the hot path; here the replay buffer is
 filled from device-resident synthetic frames (BASELINE.json config 5).  `_train` is the phase-1 step plus, per sample,
 the resampling weight get_weight(...) of the selected branch (HIP kernel lbc_phase2_weight) written back to the buffer;
-the optimizer is re-created every epoch exactly as the reference does (train_image_phase2.py:164, moments reset)."""
+the optimizer is re-created every epoch exactly as the reference does (train_image_phase2.py:164, moments reset).
+
+--replay device (default host: the loop above, unchanged) keeps the replay buffer and everything a step touches on the device
+(training/replay.py DeviceReplayBuffer, csrc/replay.hip): the weighted draw, the gather of the uint8 frames straight into the networks'
+fused u8 input pass and the weight write-back are kernels, and the loop body has no host round trip outside logging iterations.  With it
+come the reference buffer's --augment / --aug_fix_iter / --batch_aug (phase2_utils.py:191,224-234) and --save_state / --resume / --seed:
+log_dir/train_state.th after every epoch (student, buffer state, augmenter stream, RNG, (episode, epoch)); a resumed run continues with
+the next epoch bit for bit."""
 import argparse
 import ctypes
 import os
@@ -15,14 +22,17 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib
+from ..bird_view import augmenter as augmenter_mod
 from ..bird_view.models.birdview import BirdViewPolicyModelSS
 from ..bird_view.models.image import ImagePolicyModelSS
 from ..bird_view.utils import bz_utils as bzu
 from ..bird_view.utils.train_utils import one_hot
 from ..optim import FusedAdam
 from ..parallel import broadcast_module
+from . import resume
 from .native import NativeTrainer, camera_struct
 from .phase2_utils import ReplayBuffer
+from .replay import DeviceReplayBuffer
 
 BACKBONE = "resnet34"
 SAVE_EPISODES = list(range(20))
@@ -86,7 +96,140 @@ def synthetic_buffer(n_frames, device, seed=0):
     return buf
 
 
-def main(argv=None):
+# ---- --replay device ---------------------------------------------------------------------------------------------
+def synthetic_buffer_device(n_frames, device, seed=0):
+    """synthetic_buffer's frames (same generator, same order) in a DeviceReplayBuffer; the bird view as the dataset stores it, 0/255"""
+    g = torch.Generator().manual_seed(seed)
+    buf = DeviceReplayBuffer(device, buffer_limit=n_frames, seed=seed)
+    step = 1024
+    for s in range(0, n_frames, step):
+        n = min(step, n_frames - s)
+        buf.add_batch(torch.randint(0, 256, (n, 160, 384, 3), generator=g, dtype=torch.uint8),
+                      (torch.rand((n, 192, 192, 7), generator=g) < 0.1).to(torch.uint8) * 255,
+                      torch.randint(1, 5, (n,), generator=g), torch.rand(n, generator=g) * 10, [1.0] * n)
+    return buf
+
+
+def make_augmenter(config):
+    """the reference buffer's augmenter (phase2_utils.py:201-204,225-226): the recipe at the FIXED image counter aug_fix_iter"""
+    strategy = augmenter_mod.get(config.get("augment"))
+    if strategy is None:
+        return None
+    return augmenter_mod.BatchAugmenter(strategy(int(config.get("aug_fix_iter", 1000000))), seed=config["rank"])
+
+
+def _device_step(replay_buffer, trainer, config, augmenter=None):
+    """one iteration of _train_device: draw, gather (+ --batch_aug copies, + augmentation), step, write the weights back.  Everything
+    is enqueued; nothing here reads from the device.  -> (indices (B,), per-image loss (B * batch_aug,))"""
+    reps = int(config.get("batch_aug", 1) or 1)
+    idx = replay_buffer.sample_indices(config["batch_size"])
+    rgb, bv, command, speed = replay_buffer.batch(idx, reps)
+    if augmenter is not None:
+        augmenter.augment_batch(rgb)
+    if config["speed_noise"] > 0:
+        speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
+    loss = trainer.step(rgb, speed, command, birdview=bv)
+    replay_buffer.update_weights(idx, phase2_weights(trainer, trainer.last_pred[0], trainer.last_teacher[0]), reps)
+    return idx, loss
+
+
+def _state_path(config):
+    return resume._path(config["log_dir"], config["rank"])
+
+
+def save_state_device(config, net, replay_buffer, augmenter, episode, epoch):
+    """train_state.th (rank 0; train_state.rank%d.th on the others) after epoch `epoch` of episode `episode`.  The optimizer is
+    re-created at every epoch, so there are no moments to keep; synthetic frames are a function of the seed and are not written."""
+    if not config.get("save_state"):
+        return
+    device = config["device"]
+    part = {"format": 1, "phase": 2, "episode": int(episode), "epoch": int(epoch), "world_size": int(config.get("world_size", 1)),
+            "rank": int(config["rank"]), "buffer": replay_buffer.state_dict(include_frames=not config.get("synthetic_frames", True)),
+            "aug": augmenter.state_dict() if augmenter is not None else None,
+            "rng": {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device)}}
+    if config["rank"] == 0:
+        part["student"] = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+    resume._atomic_save(part, _state_path(config))
+    if config.get("world_size", 1) > 1:
+        dist.barrier()
+
+
+def load_state_device(config, trainer, replay_buffer, augmenter):
+    """-> (episode, epoch) to continue with, (0, 0) when log_dir has no state.  The student comes from rank 0's file on every rank,
+    buffer / augmenter / RNG from the rank's own."""
+    first = resume._path(config["log_dir"], 0)
+    if not config.get("resume") or not first.exists():
+        return 0, 0
+    device = config["device"]
+    state = torch.load(str(first), map_location="cpu")
+    if state.get("format") != 1 or state.get("phase") != 2:
+        raise ValueError("%s is not a phase-2 training state" % first)
+    trainer.student.load_state_dict(state["student"])
+    trainer.eng.invalidate()
+    mine = state
+    if int(state["world_size"]) != int(config.get("world_size", 1)):
+        mine = None                      # (the buffers are sharded by rank: another world size means other buffers)
+        if config["rank"] == 0:
+            print("resume: %s was written under world size %d, this run has %d: the student is restored, replay buffers, augmenter and "
+                  "random streams start fresh" % (first.name, state["world_size"], config.get("world_size", 1)))
+    elif config["rank"] != 0:
+        own = _state_path(config)
+        mine = torch.load(str(own), map_location="cpu") if own.exists() else None
+        if mine is not None and (mine["episode"], mine["epoch"]) != (state["episode"], state["epoch"]):
+            mine = None
+        if mine is None:
+            print("resume: rank %d has no buffer state of episode %d epoch %d: its buffer starts fresh" % (config["rank"], state["episode"], state["epoch"]))
+    if mine is not None:
+        if (mine["aug"] is None) != (augmenter is None):
+            raise ValueError("the state was saved %s augmentation, this run has %s" % (("without", "with") if mine["aug"] is None else ("with", "without")))
+        replay_buffer.load_state_dict(mine["buffer"])
+        if augmenter is not None:
+            augmenter.load_state_dict(mine["aug"])
+        torch.set_rng_state(mine["rng"]["cpu"])
+        torch.cuda.set_rng_state(mine["rng"]["device"], device)
+    episode, epoch = int(state["episode"]), int(state["epoch"]) + 1
+    if epoch >= config["epoch_per_episode"]:
+        episode, epoch = episode + 1, 0
+    if config["rank"] == 0:
+        print("resuming from %s: episode %d epoch %d finished" % (first, state["episode"], state["epoch"]))
+    return episode, epoch
+
+
+def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start_epoch=0, on_epoch_end=None):
+    """_train on a DeviceReplayBuffer: the same epoch, with no .cpu() / .item() / .numpy() in the loop body outside logging iterations"""
+    bs = config["batch_size"]
+    net = trainer.student
+    for epoch in range(start_epoch, config["epoch_per_episode"]):
+        trainer.opt = FusedAdam(list(net.named_parameters()), trainer.eng.grad_views, lr=config.get("lr", 1e-4),
+                                guarded=config.get("skip_nonfinite", False))                     # fresh moments each epoch
+        net.train()
+        replay_buffer.init_new_weights()
+        for i in range(len(replay_buffer) // bs):                                              # drop_last=True
+            _, loss = _device_step(replay_buffer, trainer, config, augmenter)
+            if i % int(config["log_iterations"]) == 0:
+                bzu.log.scalar(loss_mean=loss.mean().item())
+                if config.get("skip_nonfinite"):
+                    total, row = trainer.skipped()
+                    bzu.log.scalar(skipped_steps=total)
+                    if row > config["max_skipped"]:
+                        raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
+                                                 % (row, config["max_skipped"]))
+        replay_buffer.normalize_weights()                                                      # (the epoch's one read-back)
+        # the reference's eval-mode forward over the highest-weight samples (:229-250), on the trainer's own executor
+        top, rgb, bv, command, speed = replay_buffer.get_highest_k(min(32, len(replay_buffer), trainer.batch))
+        trainer.eng.forward(rgb, speed, command, False)
+        net.train()
+        bzu.log.end_epoch()
+        save_state_device(config, net, replay_buffer, augmenter, episode, epoch)
+        if on_epoch_end is not None:
+            on_epoch_end(episode, epoch, replay_buffer, trainer)
+    if episode in SAVE_EPISODES and config["rank"] == 0:
+        torch.save(net.state_dict(), str(Path(config["log_dir"]) / ("model-%d.th" % episode)))
+
+
+def main(argv=None, on_epoch_end=None):
+    """on_epoch_end(episode, epoch, replay_buffer, trainer), --replay device only: called after every epoch's state is written -- the
+    place of the reference's per-epoch evaluation / visualisation of the highest-weight samples (train_image_phase2.py:229-250)"""
     parser = argparse.ArgumentParser()
     parser.add_argument("--log_dir", required=True)
     parser.add_argument("--log_iterations", default=100)
@@ -104,7 +247,26 @@ def main(argv=None):
     parser.add_argument("--skip-nonfinite", action="store_true",
                         help="skip (on the device) every optimizer step whose gradients hold a NaN or an infinity")
     parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
+    parser.add_argument("--replay", choices=["host", "device"], default="host",
+                        help="host = the replay buffer samples on the host and builds float batches; device = buffer, weighted sampling, uint8 gather "
+                             "and weight write-back on the GPU, no host round trip inside a step")
+    parser.add_argument("--augment", choices=["None", "medium", "medium_harder", "super_hard", "custom"], default="None",
+                        help="colour augmentation of the replayed frames on the GPU (needs --replay device)")
+    parser.add_argument("--aug_fix_iter", type=int, default=1000000, help="the fixed image counter the augmentation recipe is taken at")
+    parser.add_argument("--batch_aug", type=int, default=1, help="copies of every drawn sample in a step (needs --replay device)")
+    parser.add_argument("--save_state", action="store_true", help="with --replay device: write train_state.th after every epoch")
+    parser.add_argument("--resume", action="store_true", help="with --replay device: continue from log_dir/train_state.th when there is one")
+    parser.add_argument("--seed", type=int, default=None, help="with --replay device: seed torch's generators before the networks are built")
     parsed = parser.parse_args(argv)
+    device_replay = parsed.replay == "device"
+    if not device_replay:
+        given = [f for f, on in (("--augment", parsed.augment != "None"), ("--batch_aug", parsed.batch_aug != 1), ("--save_state", parsed.save_state),
+                                 ("--resume", parsed.resume), ("--seed", parsed.seed is not None)) if on]
+        if given:
+            raise SystemExit("train_image_phase2: %s need%s --replay device (the host replay buffer has no augmentation, no --batch_aug and no "
+                             "resumable state)" % (", ".join(given), "s" if len(given) == 1 else ""))
+    if parsed.batch_aug < 1:
+        raise SystemExit("train_image_phase2: --batch_aug must be at least 1")
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         raise SystemExit("training needs a ROCm GPU")
@@ -119,8 +281,18 @@ def main(argv=None):
               "agent_args": {"camera_args": {"w": 384, "h": 160, "fov": 90, "world_y": 1.4, "fixed_offset": 4.0}}}
     if parsed.skip_nonfinite:
         config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    if device_replay:
+        config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
+                      world_size=world, synthetic_frames=True)
+        if parsed.seed is not None:
+            torch.manual_seed(parsed.seed)
+            config["seed"] = int(parsed.seed)
+        if parsed.save_state:
+            config["save_state"] = True
+        if parsed.resume:
+            config["resume"] = True
     bzu.log.init(parsed.log_dir, rank)
-    bzu.log.save_config({k: v for k, v in config.items() if k != "rank"})
+    bzu.log.save_config({k: v for k, v in config.items() if k not in ("rank", "world_size", "synthetic_frames")})
     net = ImagePolicyModelSS(BACKBONE, all_branch=True).to(device)
     if parsed.ckpt:
         net.load_state_dict(torch.load(parsed.ckpt, map_location=device))
@@ -130,8 +302,22 @@ def main(argv=None):
         teacher.load_state_dict(torch.load(parsed.teacher_path, map_location=device))
     broadcast_module(net)
     broadcast_module(teacher)
-    trainer = NativeTrainer(net, teacher, parsed.batch_size, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
+    trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
                             camera=camera_struct(), skip_nonfinite=bool(parsed.skip_nonfinite))
+    if device_replay:
+        buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
+        if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
+            buf.reseed(parsed.seed * 7919 + rank)
+        aug = make_augmenter(config)
+        episode0, epoch0 = load_state_device(config, trainer, buf, aug)
+        for episode in range(episode0, int(parsed.max_episode)):
+            t0 = time.time()
+            _train_device(buf, trainer, config, episode, aug, epoch0 if episode == episode0 else 0, on_epoch_end)
+            if rank == 0:
+                print("episode %d: %.1f s" % (episode, time.time() - t0))
+        if world > 1:
+            dist.destroy_process_group()
+        return {"net": net, "buffer": buf, "trainer": trainer}
     buf = synthetic_buffer(parsed.synthetic // world, device, seed=rank)
     for episode in range(int(parsed.max_episode)):
         t0 = time.time()
