@@ -33,6 +33,8 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  * 201: lbc_conv_desc.bf16 = 4 / lbc_net_desc.precision = 3.  Later, without a new number: lbc_adam_state, lbc_adam_state_bytes,
  *      lbc_adam_step_guarded -- exports were only ADDED, every 201 host stays valid against this library, and a host that needs the
  *      guarded step finds out with dlsym (the Python binding fails on the missing symbol when it declares its signatures).
+ *      Later again, the same way: lbc_adam_clip_state, lbc_adam_clip_state_bytes, lbc_adam_step_clipped (a new record type and
+ *      new exports; lbc_adam_state and the guarded step are unchanged).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -249,6 +251,41 @@ typedef struct lbc_adam_state {
 size_t lbc_adam_state_bytes(void);
 int lbc_adam_step_guarded(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
                           double eps, double weight_decay, lbc_adam_state* state_dev, lbc_stream_t stream);
+
+/* Guarded Adam with gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, which the reference does not call): the
+ * pass that looks for NaN / +-Inf also sums the squares of the gradients, so the global L2 norm, the clipping coefficient and
+ * the skip decision are all taken on the device, again without a device-to-host copy or a synchronisation.
+ * The record is lbc_adam_clip_state_bytes(nchunks) bytes of device memory owned by the caller: the header below followed by one
+ * double per chunk (the chunks' partial sums of squares, scratch).  Same contract as the guarded step: ZERO-filled once, 8-byte
+ * aligned, never written by the host while steps are in flight; to resume, upload a header that carries the saved counters
+ * (step, skipped_*, clipped_total) and zeros elsewhere.
+ * One call enqueues, in order: the norm pass (reads exactly the n elements of every chunk once; per chunk a sum of exact f64
+ * squares, combined in a fixed order -- no atomics, so the same gradients give the same 8 bytes of grad_norm on every run and
+ * every rank), one bookkeeping workgroup (adds the partials in a fixed order, then the bookkeeping of the guarded step; on a
+ * clean step grad_norm = sqrt(sum) and
+ *     clip_coef = (max_norm > 0 && max_norm / (grad_norm + 1e-6) < 1) ? (float)(max_norm / (grad_norm + 1e-6)) : 1.0f,
+ * clipped_total += clip_coef < 1; on a skipped step all three keep the values of the last clean step), and the update: the
+ * guarded update on g * clip_coef, the product rounded to f32 on its own.  With clip_coef == 1 the step is bit for bit
+ * lbc_adam_step_guarded; with clip_coef < 1 it is lbc_adam_step_guarded on gradients multiplied by that float.
+ * THE GRADIENT BUFFER IS NOT WRITTEN: g keeps the unclipped values (clipping costs no store of the gradients).
+ * max_norm <= 0 measures the norm without clipping; a NaN max_norm is refused.  Under data parallelism call it after the
+ * gradient all-reduce: every rank derives the same coefficient from the same bytes. */
+typedef struct lbc_adam_clip_state {
+    long long step;              /* the fields of lbc_adam_state, same meaning and offsets */
+    long long skipped_total;
+    long long skipped_in_a_row;
+    int bad;
+    int scan_flag;
+    float lr_over_bc1;
+    float inv_bc2_sqrt;
+    double grad_norm;            /* global L2 norm of the gradients of the last clean step (before clipping) */
+    float clip_coef;             /* what the last clean step multiplied its gradients by; 1 = not clipped */
+    int reserved;                /* zero */
+    long long clipped_total;     /* applied steps with clip_coef < 1 since the record was zeroed */
+} lbc_adam_clip_state;
+size_t lbc_adam_clip_state_bytes(int nchunks);
+int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, lbc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-operator entry points of the HBM-bound kernels: what the executor above launches between the

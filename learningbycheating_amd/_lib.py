@@ -57,6 +57,13 @@ class AdamState(ctypes.Structure):
                 ("bad", c_int), ("scan_flag", c_int), ("lr_over_bc1", c_float), ("inv_bc2_sqrt", c_float)]
 
 
+class AdamClipState(ctypes.Structure):
+    """lbc_adam_clip_state: the header of the clipped step's device record (lbc_adam_state's fields, then norm / coefficient / count);
+    lbc_adam_clip_state_bytes(nchunks) - sizeof(this) bytes of per-chunk partial sums follow it on the device"""
+    _fields_ = AdamState._fields_ + [("grad_norm", ctypes.c_double), ("clip_coef", c_float), ("reserved", c_int),
+                                     ("clipped_total", ctypes.c_longlong)]
+
+
 _SIGNATURES = {
     "lbc_last_error": (c_char_p, []),
     "lbc_backend": (c_char_p, []),
@@ -98,6 +105,8 @@ _SIGNATURES = {
     "lbc_adam_step": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 5 + [c_int, c_void_p]),
     "lbc_adam_state_bytes": (c_size_t, []),
     "lbc_adam_step_guarded": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 5 + [c_void_p, c_void_p]),
+    "lbc_adam_clip_state_bytes": (c_size_t, [c_int]),
+    "lbc_adam_step_clipped": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 6 + [c_void_p, c_void_p]),
     "lbc_bn_stats": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "lbc_bn_finalize_stats": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 5),
     "lbc_bn_apply_relu_add_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),

@@ -28,6 +28,17 @@ int lbc_adam_step_guarded(const lbc_adam_chunk* chunks_dev, int nchunks, double 
                                    state_dev, (hipStream_t)stream);
 }
 
+size_t lbc_adam_clip_state_bytes(int nchunks) { return sizeof(lbc_adam_clip_state) + sizeof(double) * (size_t)(nchunks > 0 ? nchunks : 0); }
+
+int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_adam_clip_state) == 64 && offsetof(lbc_adam_clip_state, grad_norm) == sizeof(lbc_adam_state) &&
+                  offsetof(lbc_adam_clip_state, clipped_total) == 56, "lbc_adam_clip_state layout (include/lbc_hip.h)");
+    return lbc_adam_clipped_launch(reinterpret_cast<const AdamChunk*>(chunks_dev), nchunks, lr, beta1, beta2, eps, weight_decay,
+                                   max_norm, state_dev, (hipStream_t)stream);
+}
+
 // Every entry point that takes a descriptor checks it: struct_size must cover the fields of the first checked layout (ABI 200: everything up to
 // and including split_workspace_bytes) and must not exceed this library's struct.  A host built against an OLDER header of the same major
 // ABI (fewer trailing fields) stays valid: whoever appends a field must read it only where struct_size covers it (today the checked

@@ -271,3 +271,8 @@ long long lbc_adam_profile_elems_get();      // what lbc_adam_profile_elems() wa
 struct lbc_adam_state;
 int lbc_adam_guarded_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, lbc_adam_state* state_dev, hipStream_t s);
+// adam_clip.hip: the guarded step whose gradient pass also sums the squares -> global norm, clipping coefficient and skip decision on
+// the device record (include/lbc_hip.h lbc_adam_clip_state + one double per chunk) -> the guarded update on g * clip_coef.
+struct lbc_adam_clip_state;
+int lbc_adam_clipped_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, hipStream_t s);

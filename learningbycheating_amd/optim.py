@@ -19,12 +19,25 @@ class FusedAdam:
     record (lbc_adam_state), no step ever syncs; `step_count` and `skipped()` read the record back (a device-to-host copy: for logging
     and checkpoints only).
 
+    max_grad_norm=X (a number; implies guarded): the gradient pass of the guard also sums the squares (csrc/adam_clip.hip), and the update
+    multiplies every gradient element by torch.nn.utils.clip_grad_norm_'s coefficient min(1, X / (norm + 1e-6)), all on the device and
+    still without a sync.  X = 0 measures the norm and never clips.  THE GRADIENT VIEWS KEEP THE UNCLIPPED VALUES: the coefficient is
+    applied inside the update, the gradient buffer is not written.  `grad_stats()` reads norm, coefficient and the number of clipped
+    steps back (a sync, like `skipped()`).  None (the default) leaves the two paths above exactly as they are.  The attribute
+    `max_grad_norm` of a clipped optimizer may be assigned another number between steps: step() passes its current value with every
+    call (the choice between the clipped and the other paths is made once, here).
+
     state_dict() / load_state_dict() speak torch.optim.Adam's own format (moments in the parameters' logical shapes, parameters indexed
     in named_parameters() order), so a sidecar written here loads into a torch.optim.Adam over the reference-layout module and back."""
 
-    def __init__(self, named_params, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, guarded=False):
+    def __init__(self, named_params, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, guarded=False,
+                 max_grad_norm=None):
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.guarded = bool(guarded)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if self.max_grad_norm is not None and self.max_grad_norm != self.max_grad_norm:
+            raise ValueError("FusedAdam: max_grad_norm is NaN")
+        self.clipped = self.max_grad_norm is not None
+        self.guarded = bool(guarded) or self.clipped
         self._step_count = 0
         self.all_names = [n for n, _ in named_params]
         self.names = [n for n, _ in named_params if n in grads]
@@ -58,13 +71,23 @@ class FusedAdam:
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
         self._keep = (params, grads)
         self.record = None
-        if self.guarded:
+        self._State = _lib.AdamClipState if self.clipped else _lib.AdamState
+        if self.clipped:
+            nbytes = int(_lib.get().lbc_adam_clip_state_bytes(self.nchunks))       # the header + one partial sum of squares per chunk
+            assert nbytes == ctypes.sizeof(_lib.AdamClipState) + 8 * self.nchunks, "lbc_adam_clip_state layout"
+            self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        elif self.guarded:
             nbytes = int(_lib.get().lbc_adam_state_bytes())
             assert nbytes == ctypes.sizeof(_lib.AdamState), "lbc_adam_state layout"
             self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)       # (torch allocations are 256-byte aligned)
 
     # ---- the step ---------------------------------------------------------------------------
     def step(self):
+        if self.clipped:
+            _lib.check(_lib.get().lbc_adam_step_clipped(_lib.ptr(self.table), self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                        self.weight_decay, self.max_grad_norm, _lib.ptr(self.record),
+                                                        _lib.stream_for(self.table)), "adam_step_clipped")
+            return
         if self.guarded:
             _lib.check(_lib.get().lbc_adam_step_guarded(_lib.ptr(self.table), self.nchunks, self.lr, self.betas[0], self.betas[1], self.eps,
                                                         self.weight_decay, _lib.ptr(self.record), _lib.stream_for(self.table)), "adam_step_guarded")
@@ -74,12 +97,19 @@ class FusedAdam:
                                             self.weight_decay, self._step_count, _lib.stream_for(self.table)), "adam_step")
 
     def _read_record(self):
-        return _lib.AdamState.from_buffer_copy(self.record.cpu().numpy().tobytes())       # (the copy waits for the steps in flight)
+        head = self.record[:ctypes.sizeof(self._State)]
+        return self._State.from_buffer_copy(head.cpu().numpy().tobytes())       # (the copy waits for the steps in flight)
 
-    def _write_record(self, step, skipped_total=0, skipped_in_a_row=0):
+    def _write_record(self, step, skipped_total=0, skipped_in_a_row=0, clipped_total=None):
         # the coefficients stay zero: the bookkeeping kernel derives them from `step` before the next applied update reads them
-        rec = _lib.AdamState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0)
-        self.record.copy_(torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8))
+        if self.clipped:
+            # norm and coefficient of the last clean step are telemetry: they are kept, as is the count unless a new one is given
+            old = self._read_record()
+            rec = _lib.AdamClipState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0, old.grad_norm, old.clip_coef, 0,
+                                     int(old.clipped_total if clipped_total is None else clipped_total))
+        else:
+            rec = _lib.AdamState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0)
+        self.record[:ctypes.sizeof(rec)].copy_(torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8))
 
     @property
     def step_count(self):
@@ -104,6 +134,20 @@ class FusedAdam:
     def set_skipped(self, total, in_a_row):
         if self.guarded:
             self._write_record(self._read_record().step, total, in_a_row)
+
+    def grad_stats(self):
+        """{"grad_norm", "clip_coef", "clipped_total"} of the clipped mode: global L2 norm of the gradients (before clipping) and the
+        coefficient of the last applied step, number of applied steps that were clipped.  Reads the device record: a sync, for logging
+        and checkpoints only.  Without max_grad_norm the optimizer measures nothing: None / 1.0 / 0."""
+        if not self.clipped:
+            return {"grad_norm": None, "clip_coef": 1.0, "clipped_total": 0}
+        r = self._read_record()
+        return {"grad_norm": float(r.grad_norm), "clip_coef": float(r.clip_coef), "clipped_total": int(r.clipped_total)}
+
+    def set_clipped(self, total):
+        if self.clipped:
+            r = self._read_record()
+            self._write_record(r.step, r.skipped_total, r.skipped_in_a_row, clipped_total=total)
 
     def state_of(self, name):
         off, n = self.offsets[name]

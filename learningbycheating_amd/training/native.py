@@ -34,10 +34,16 @@ class NativeTrainer:
     wire, every rank reads the same reduced bytes, so every rank takes the same decision with no extra collective.
     `skipped()` -> (total, in a row) reads the device counters (a sync: call it where the loop syncs anyway).
 
+    max_grad_norm=X (a number; implies the guard): the same device pass also measures the global L2 norm of the (all-reduced) gradients,
+    and the update applies torch.nn.utils.clip_grad_norm_'s coefficient min(1, X / (norm + 1e-6)); X = 0 measures without clipping.
+    It sits where the guarded step sits, behind StageAllReducer.wait(): every rank sums the same reduced bytes in the same fixed order,
+    so every rank derives the same coefficient, bit for bit, with no extra collective.  The gradient buffer is not written: `eng.grad_views`
+    keep the UNCLIPPED values.  `grad_stats()` -> {"grad_norm", "clip_coef", "clipped_total"} reads the device record (a sync).
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
-                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False):
+                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False, max_grad_norm=None):
         self.student, self.teacher, self.phase, self.batch, self.world = student, teacher, phase, batch, world_size
         self.device = device
         student.train()
@@ -51,8 +57,10 @@ class NativeTrainer:
             self.teng.set_frozen(True)
             self._teacher_versions = self._versions(teacher)
         self.cam = camera or camera_struct()
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.opt = FusedAdam(list(student.named_parameters()), self.eng.grad_views, lr=lr, guarded=self.skip_nonfinite)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite) or max_grad_norm is not None
+        self.opt = FusedAdam(list(student.named_parameters()), self.eng.grad_views, lr=lr, guarded=self.skip_nonfinite,
+                             max_grad_norm=max_grad_norm)
         self.reducer = StageAllReducer(self.eng.grad_flat, self.eng.grad_spans, group, grad_dtype=grad_dtype)   # grad_dtype: see parallel.py
         self.sync_bn = bool(sync_bn and world_size > 1)
         if sync_bn and world_size > 1:
@@ -146,19 +154,23 @@ class NativeTrainer:
     def skipped(self):
         return self.opt.skipped()
 
+    def grad_stats(self):
+        return self.opt.grad_stats()
+
     def _layout(self):
         return [[n, list(p.shape)] for n, p in self.student.named_parameters()]
 
     def state_dict(self):
         """student state_dict (parameters + BatchNorm buffers, CPU copies), the optimizer in torch.optim.Adam's format, the guard's
-        counters, and what the state was produced under (phase, parameter layout, precision, world size).  The frozen teacher is not
-        part of it: the scripts load it from its own checkpoint.  Syncs the device."""
+        counters (with the number of clipped steps), and what the state was produced under (phase, parameter layout, precision, world
+        size).  The frozen teacher is not part of it: the scripts load it from its own checkpoint.  Syncs the device."""
         total, row = self.opt.skipped()
         return {"format": 1, "phase": self.phase, "precision": getattr(self.student, "precision", "fp32"), "world_size": int(self.world),
                 "layout": self._layout(),
                 "student": {k: v.detach().cpu().clone() for k, v in self.student.state_dict().items()},
                 "optimizer": self.opt.state_dict(),
-                "guard": {"enabled": self.skip_nonfinite, "skipped_total": total, "skipped_in_a_row": row}}
+                "guard": {"enabled": self.skip_nonfinite, "skipped_total": total, "skipped_in_a_row": row,
+                          "clipped_total": self.opt.grad_stats()["clipped_total"]}}
 
     def load_state_dict(self, sd):
         """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size or precision
@@ -184,5 +196,6 @@ class NativeTrainer:
         self.opt.load_state_dict(sd["optimizer"])
         g = sd.get("guard") or {}
         self.opt.set_skipped(g.get("skipped_total", 0), g.get("skipped_in_a_row", 0))
+        self.opt.set_clipped(g.get("clipped_total", 0))
         self.eng.invalidate()
         return notes

@@ -1,4 +1,4 @@
-"""What the training scripts share for --save_state / --resume / --skip-nonfinite.
+"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -26,6 +26,36 @@ def add_arguments(parser, with_resume=True):
                         help="skip (on the device, without a host round trip) every optimizer step whose gradients hold a NaN or an infinity")
     parser.add_argument("--max-skipped", type=int, default=50,
                         help="with --skip-nonfinite: abort when more steps than this were skipped in a row (checked on logging iterations)")
+    add_clip_arguments(parser)
+
+
+def add_clip_arguments(parser):
+    parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                        help="clip the gradients to global L2 norm X (torch.nn.utils.clip_grad_norm_) on the device, inside the optimizer "
+                             "step; implies --skip-nonfinite.  Default: off")
+    parser.add_argument("--log-grad-norm", action="store_true",
+                        help="measure the global gradient norm on the device without clipping (implies --skip-nonfinite); logging "
+                             "iterations report grad_norm, clip_coef and clipped_steps")
+
+
+def clip_entries(parsed):
+    """config entries of --clip-grad-norm / --log-grad-norm: max_grad_norm (0 = measure only) plus the guard they imply"""
+    if parsed.clip_grad_norm is not None:
+        if not parsed.clip_grad_norm > 0:
+            raise SystemExit("--clip-grad-norm needs a positive norm (use --log-grad-norm to measure without clipping)")
+        return {"max_grad_norm": float(parsed.clip_grad_norm), "skip_nonfinite": True, "max_skipped": int(parsed.max_skipped)}
+    if parsed.log_grad_norm:
+        return {"max_grad_norm": 0.0, "skip_nonfinite": True, "max_skipped": int(parsed.max_skipped)}
+    return {}
+
+
+def log_grad_stats(config, trainer, log_scalar, **tags):
+    """on a logging iteration of a run with --clip-grad-norm / --log-grad-norm: grad_norm, clip_coef and clipped_steps (a sync)"""
+    if config.get("max_grad_norm") is None:
+        return None
+    st = trainer.grad_stats()
+    log_scalar(grad_norm=st["grad_norm"], clip_coef=st["clip_coef"], clipped_steps=st["clipped_total"], **tags)
+    return st
 
 
 def config_entries(parsed):
@@ -41,6 +71,7 @@ def config_entries(parsed):
         out["resume"] = True
     if parsed.skip_nonfinite:
         out.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    out.update(clip_entries(parsed))
     return out
 
 

@@ -34,6 +34,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             skipped = resume.check_skipped(config, trainer, "train_birdview") if is_train else None
             if skipped is not None:
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
+            if is_train:
+                resume.log_grad_stats(config, trainer, bzu.log.scalar, is_train=is_train)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
@@ -59,7 +61,8 @@ def train(config):
     bs = config["data_args"]["batch_size"]
     data_train, data_val = make_loaders(config, device, rank, world)
     trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world,
-                            skip_nonfinite=config.get("skip_nonfinite", False))
+                            skip_nonfinite=config.get("skip_nonfinite", False),
+                            max_grad_norm=config.get("max_grad_norm"))
     loaders = {"train": data_train, "val": data_val}
     # --resume: the full state (train_state.th: optimizer, loaders, RNG, epoch) when there is one; without it, as before, the newest
     # model-%d.th with a fresh Adam from epoch 0

@@ -40,6 +40,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             skipped = resume.check_skipped(config, trainer, "phase 0") if is_train else None
             if skipped is not None:
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
+            if is_train:
+                resume.log_grad_stats(config, trainer, bzu.log.scalar, is_train=is_train)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
@@ -68,7 +70,8 @@ def train(config):
     data_train, data_val = make_loaders(config, device, rank, world)
     cam = camera_struct(**{k: float(v) for k, v in config["camera_args"].items()})
     trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
-                            skip_nonfinite=config.get("skip_nonfinite", False))
+                            skip_nonfinite=config.get("skip_nonfinite", False),
+                            max_grad_norm=config.get("max_grad_norm"))
     loaders = {"train": data_train, "val": data_val}
     state = resume.load(config, trainer, loaders)
     for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):

@@ -46,13 +46,32 @@ def phase2_weights(trainer, p_sel, t_sel):
     return w
 
 
+def _fresh_optimizer(trainer, config, lr):
+    """fresh moments each epoch, as the reference re-creates its Adam there.  With --clip-grad-norm / --log-grad-norm the number of
+    clipped steps goes on counting across the epochs of a run (read and written at the epoch boundary, where the loop syncs anyway)."""
+    clipped = trainer.opt.grad_stats()["clipped_total"]
+    trainer.opt = FusedAdam(list(trainer.student.named_parameters()), trainer.eng.grad_views, lr=lr,
+                            guarded=config.get("skip_nonfinite", False), max_grad_norm=config.get("max_grad_norm"))
+    trainer.opt.set_clipped(clipped)
+
+
+def _log_guard(trainer, config):
+    """on a logging iteration: skipped_steps (and the abort on a run of them), grad_norm / clip_coef / clipped_steps"""
+    if config.get("skip_nonfinite"):
+        total, row = trainer.skipped()
+        bzu.log.scalar(skipped_steps=total)
+        if row > config["max_skipped"]:
+            raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
+                                     % (row, config["max_skipped"]))
+    resume.log_grad_stats(config, trainer, bzu.log.scalar)
+
+
 def _train(replay_buffer, trainer, config, episode):
     device = config["device"]
     bs = config["batch_size"]
     net, teacher_net = trainer.student, trainer.teacher
     for epoch in range(config["epoch_per_episode"]):
-        trainer.opt = FusedAdam(list(net.named_parameters()), trainer.eng.grad_views, lr=1e-4,
-                                guarded=config.get("skip_nonfinite", False))                     # fresh moments each epoch
+        _fresh_optimizer(trainer, config, 1e-4)
         net.train()
         replay_buffer.init_new_weights()
         for i in range(len(replay_buffer) // bs):                                              # drop_last=True
@@ -65,12 +84,7 @@ def _train(replay_buffer, trainer, config, episode):
             replay_buffer.update_weights(idx, phase2_weights(trainer, trainer.last_pred[0], trainer.last_teacher[0]))
             if i % int(config["log_iterations"]) == 0:
                 bzu.log.scalar(loss_mean=loss.mean().item())
-                if config.get("skip_nonfinite"):
-                    total, row = trainer.skipped()
-                    bzu.log.scalar(skipped_steps=total)
-                    if row > config["max_skipped"]:
-                        raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
-                                                 % (row, config["max_skipped"]))
+                _log_guard(trainer, config)
         replay_buffer.normalize_weights()
         # the reference evaluates (eval mode) and visualises the 32 highest-weight samples here (:229-250); visualisation
         # is outside the hot path, the forward is kept so that the same kernels run
@@ -200,20 +214,14 @@ def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start
     bs = config["batch_size"]
     net = trainer.student
     for epoch in range(start_epoch, config["epoch_per_episode"]):
-        trainer.opt = FusedAdam(list(net.named_parameters()), trainer.eng.grad_views, lr=config.get("lr", 1e-4),
-                                guarded=config.get("skip_nonfinite", False))                     # fresh moments each epoch
+        _fresh_optimizer(trainer, config, config.get("lr", 1e-4))
         net.train()
         replay_buffer.init_new_weights()
         for i in range(len(replay_buffer) // bs):                                              # drop_last=True
             _, loss = _device_step(replay_buffer, trainer, config, augmenter)
             if i % int(config["log_iterations"]) == 0:
                 bzu.log.scalar(loss_mean=loss.mean().item())
-                if config.get("skip_nonfinite"):
-                    total, row = trainer.skipped()
-                    bzu.log.scalar(skipped_steps=total)
-                    if row > config["max_skipped"]:
-                        raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
-                                                 % (row, config["max_skipped"]))
+                _log_guard(trainer, config)
         replay_buffer.normalize_weights()                                                      # (the epoch's one read-back)
         # the reference's eval-mode forward over the highest-weight samples (:229-250), on the trainer's own executor
         top, rgb, bv, command, speed = replay_buffer.get_highest_k(min(32, len(replay_buffer), trainer.batch))
@@ -247,6 +255,7 @@ def main(argv=None, on_epoch_end=None):
     parser.add_argument("--skip-nonfinite", action="store_true",
                         help="skip (on the device) every optimizer step whose gradients hold a NaN or an infinity")
     parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
+    resume.add_clip_arguments(parser)
     parser.add_argument("--replay", choices=["host", "device"], default="host",
                         help="host = the replay buffer samples on the host and builds float batches; device = buffer, weighted sampling, uint8 gather "
                              "and weight write-back on the GPU, no host round trip inside a step")
@@ -281,6 +290,7 @@ def main(argv=None, on_epoch_end=None):
               "agent_args": {"camera_args": {"w": 384, "h": 160, "fov": 90, "world_y": 1.4, "fixed_offset": 4.0}}}
     if parsed.skip_nonfinite:
         config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    config.update(resume.clip_entries(parsed))
     if device_replay:
         config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
                       world_size=world, synthetic_frames=True)
@@ -303,7 +313,8 @@ def main(argv=None, on_epoch_end=None):
     broadcast_module(net)
     broadcast_module(teacher)
     trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
-                            camera=camera_struct(), skip_nonfinite=bool(parsed.skip_nonfinite))
+                            camera=camera_struct(), skip_nonfinite=config.get("skip_nonfinite", False),
+                            max_grad_norm=config.get("max_grad_norm"))
     if device_replay:
         buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
