@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE ONLY: builds (on demand) and loads the CPU-emulated build of the HIP
 kernel sources (see tests/emu/include/hip/hip_runtime.h) and injects it into the package loader."""
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -10,7 +11,10 @@ EMU_LIB = os.path.join(HERE, "liblbc_emu.so")
 
 
 def build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "learningbycheating_amd", "csrc"), "emu"])
+    # one make at a time: pytest-xdist workers on a clean tree would otherwise link the library under each other's feet
+    with open(EMU_LIB + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "learningbycheating_amd", "csrc"), "emu"])
     return EMU_LIB
 
 

@@ -5,8 +5,8 @@ costs three bf16 MFMAs (lo*hi + hi*lo + hi*hi) into the f32 accumulator.  Tensor
 
 Kernel parity is checked two ways on the same inputs: (a) against a float64 torch result on the UNROUNDED operands, and (b) against
 precision 1 (operands rounded to bf16 once), whose error must be >= 50x larger -- the check that fails if a lo product is dropped or a
-lo plane is mis-addressed (either leaves bf16-level error behind).  Small shapes run the kernel sources under the CPU emulator; the
-gpu-marked cases run the real gfx950 library at layer shapes."""
+lo plane is mis-addressed (either leaves bf16-level error behind).  Small shapes run the kernel sources under the CPU emulator and, as
+"-gfx950" cases, the real gfx950 library; the other gpu-marked cases run that library at layer shapes."""
 import ctypes
 import os
 
@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from learningbycheating_amd import WAYPOINT_MEAN_TOLERANCE, WAYPOINT_TOLERANCE, _lib
 from oracle import lbc_oracle as O
-from tests.helpers import Conv, engine_from_state_dict, relerr
+from tests.helpers import WHERE, Conv, engine_from_state_dict, on_both, relerr
 from tests.test_kernels import BF_REAL, BF_SMALL, make
 from tests.test_model import _diag, _frozen_gradient_check, _inputs, _launch_counts, seeded_inputs
 from tests.test_step import _k_steps
@@ -55,7 +55,7 @@ def _bn_on_load(x, C, seed):
     return ps, pt, F.relu(x.double() * ps.double().view(1, -1, 1, 1) + pt.double().view(1, -1, 1, 1))
 
 
-@pytest.mark.parametrize("cfg", BF_SMALL + BF_REAL)
+@pytest.mark.parametrize("cfg", on_both("cfg", BF_SMALL, BF_REAL))
 def test_conv_fwd_x3(env, cfg):
     """forward with BatchNorm+ReLU on load (f32, before the split) and the statistics partials"""
     dev, _ = env
@@ -71,8 +71,8 @@ def test_conv_fwd_x3(env, cfg):
 
 
 @pytest.mark.parametrize("cfgid", [0, 1, 2])
-@pytest.mark.parametrize("cfg", [(2, 9, 8, 128, 128, 3, 1, 1), (1, 10, 12, 64, 128, 3, 2, 1)] +
-                         [pytest.param((32, 20, 48, 128, 128, 3, 1, 1), marks=gpu), pytest.param((32, 10, 24, 256, 512, 1, 2, 0), marks=gpu)])
+@pytest.mark.parametrize("cfg", on_both("cfg", [(2, 9, 8, 128, 128, 3, 1, 1), (1, 10, 12, 64, 128, 3, 2, 1)],
+                                         [pytest.param((32, 20, 48, 128, 128, 3, 1, 1), marks=gpu), pytest.param((32, 10, 24, 256, 512, 1, 2, 0), marks=gpu)]))
 def test_conv_x3_every_tile_config(env, cfg, cfgid, lbc_config):
     """the three register-staged tile shapes (128 x 64, 128 x 128, 64 x 64; LBC_FORCE_CFG pins the policy) in both GEMM orientations:
     forward (gather) with bias + residual + ReLU, and the input gradient (transposed) through the depth-contiguous weight copy"""
@@ -96,7 +96,8 @@ def test_conv_x3_every_tile_config(env, cfg, cfgid, lbc_config):
     _check("dgrad cfg %d %s" % (cfgid, cfg), dx3, dx1, ref)
 
 
-def test_conv_fwd_x3_residual_relu(env):
+@pytest.mark.parametrize("where", WHERE)
+def test_conv_fwd_x3_residual_relu(env, where):
     dev, _ = env
     cfg = (2, 6, 8, 64, 64, 3, 1, 1)
     x, w = make(cfg, 140)
@@ -106,7 +107,7 @@ def test_conv_fwd_x3_residual_relu(env):
     _check("fwd residual", y3, y1, ref)
 
 
-@pytest.mark.parametrize("cfg", BF_SMALL[:3] + [pytest.param((4, 20, 48, 128, 128, 3, 1, 1), marks=gpu), pytest.param((2, 20, 48, 128, 256, 3, 2, 1), marks=gpu)])
+@pytest.mark.parametrize("cfg", on_both("cfg", BF_SMALL[:3], [pytest.param((4, 20, 48, 128, 128, 3, 1, 1), marks=gpu), pytest.param((2, 20, 48, 128, 256, 3, 2, 1), marks=gpu)]))
 def test_conv_dgrad_x3(env, cfg):
     """input gradient (+ the identity gradient in the epilogue), stride 1 and the four-phase stride-2 launch"""
     dev, _ = env
@@ -121,7 +122,7 @@ def test_conv_dgrad_x3(env, cfg):
     _check("dgrad %s" % (cfg,), dx3, dx1, xg.grad + r.double())
 
 
-@pytest.mark.parametrize("cfg", BF_SMALL + [(40, 5, 6, 64, 64, 3, 1, 1)] + BF_REAL)
+@pytest.mark.parametrize("cfg", on_both("cfg", BF_SMALL + [(40, 5, 6, 64, 64, 3, 1, 1)], BF_REAL))
 def test_conv_wgrad_x3(env, cfg):
     dev, _ = env
     N, H, W, C, K, k, s, p = cfg
@@ -134,7 +135,7 @@ def test_conv_wgrad_x3(env, cfg):
     _check("wgrad %s" % (cfg,), dw3, dw1, wg.grad)
 
 
-@pytest.mark.parametrize("cfg", [(3, 6, 8, 64, 128, 3, 1, 1), pytest.param((8, 20, 48, 128, 128, 3, 1, 1), marks=gpu)])
+@pytest.mark.parametrize("cfg", on_both("cfg", [(3, 6, 8, 64, 128, 3, 1, 1)], [pytest.param((8, 20, 48, 128, 128, 3, 1, 1), marks=gpu)]))
 def test_conv_wgrad_x3_bn_relu_on_load(env, cfg):
     """conv2's weight gradient: y1 read with bn1 + ReLU applied on load (f32, before the split)"""
     dev, _ = env
@@ -149,7 +150,7 @@ def test_conv_wgrad_x3_bn_relu_on_load(env, cfg):
     _check("wgrad bn-on-load %s" % (cfg,), dw3, dw1, wg.grad)
 
 
-@pytest.mark.parametrize("cfg", [(2, 3, 4, 64, 64), (1, 5, 12, 128, 64)] + [pytest.param((4, 5, 12, 640, 256), marks=gpu), pytest.param((2, 20, 48, 128, 64), marks=gpu)])
+@pytest.mark.parametrize("cfg", on_both("cfg", [(2, 3, 4, 64, 64), (1, 5, 12, 128, 64)], [pytest.param((4, 5, 12, 640, 256), marks=gpu), pytest.param((2, 20, 48, 128, 64), marks=gpu)]))
 def test_deconv_x3(env, cfg):
     """lbc_deconv3x3s2_fwd (four output-parity phases in one launch, BatchNorm on load, bias, ReLU, statistics), _dgrad, _wgrad"""
     dev, _ = env
@@ -173,7 +174,8 @@ def test_deconv_x3(env, cfg):
     _check("deconv wgrad %s" % (cfg,), dw3, dw1, wd.grad)
 
 
-def test_mode4_descriptor_decoding(env):
+@pytest.mark.parametrize("where", WHERE)
+def test_mode4_descriptor_decoding(env, where):
     """bf16 = 4 is its own mode: f32 tensors (a mode read as 'bf16 tensors' would have refused the f32 weight layout or read half the
     bytes), no grouped weight gradient; the modes around it decode as before"""
     dev, _ = env
