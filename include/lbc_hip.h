@@ -34,7 +34,8 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      lbc_adam_step_guarded -- exports were only ADDED, every 201 host stays valid against this library, and a host that needs the
  *      guarded step finds out with dlsym (the Python binding fails on the missing symbol when it declares its signatures).
  *      Later again, the same way: lbc_adam_clip_state, lbc_adam_clip_state_bytes, lbc_adam_step_clipped (a new record type and
- *      new exports; lbc_adam_state and the guarded step are unchanged).
+ *      new exports; lbc_adam_state and the guarded step are unchanged).  And once more: lbc_grad_accumulate (one new export, no
+ *      record, nothing existing changed).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -286,6 +287,16 @@ typedef struct lbc_adam_clip_state {
 size_t lbc_adam_clip_state_bytes(int nchunks);
 int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
                           double eps, double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, lbc_stream_t stream);
+
+/* Gradient accumulation over micro-batches (what the reference would get from calling loss.backward() K times before
+ * optimizer.step(); it never does): lbc_net_backward overwrites the bound gradients, so a caller that wants the sum of K backward
+ * passes adds each one (or each stage's range of it, right behind that stage) into a buffer of its own, and points the optimizer's
+ * chunk table and the gradient all-reduce at that buffer.
+ * acc[i] = first ? g[i] : acc[i] + g[i], i < n.  first != 0 never READS acc (a NaN left there by a skipped window cannot survive).
+ * g, acc: device f32, 16-byte aligned (LBC_EINVAL otherwise, nothing launched); the two ranges must NOT overlap (g == acc included:
+ * the kernel reads and writes through restrict-qualified pointers); n >= 0, n == 0 launches nothing.  One f32 add per
+ * element in call order: no atomics, no reassociation -- the same inputs give the same bits on every run and every rank. */
+int lbc_grad_accumulate(const float* g, float* acc, long long n, int first, lbc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-operator entry points of the HBM-bound kernels: what the executor above launches between the

@@ -39,6 +39,11 @@ int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double 
                                    max_norm, state_dev, (hipStream_t)stream);
 }
 
+int lbc_grad_accumulate(const float* g, float* acc, long long n, int first, lbc_stream_t stream)
+{
+    return lbc_grad_accumulate_launch(g, acc, n, first, (hipStream_t)stream);
+}
+
 // Every entry point that takes a descriptor checks it: struct_size must cover the fields of the first checked layout (ABI 200: everything up to
 // and including split_workspace_bytes) and must not exceed this library's struct.  A host built against an OLDER header of the same major
 // ABI (fewer trailing fields) stays valid: whoever appends a field must read it only where struct_size covers it (today the checked

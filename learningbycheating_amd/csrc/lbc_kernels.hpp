@@ -276,3 +276,5 @@ int lbc_adam_guarded_launch(const AdamChunk* chunks_dev, int nchunks, double lr,
 struct lbc_adam_clip_state;
 int lbc_adam_clipped_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, hipStream_t s);
+// grad_accum.hip: acc = first ? g : acc + g over n floats (gradient accumulation over micro-batches); one launch, no atomics
+int lbc_grad_accumulate_launch(const float* g, float* acc, long long n, int first, hipStream_t s);

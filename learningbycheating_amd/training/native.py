@@ -10,7 +10,7 @@ import torch
 from .. import _lib
 from ..engine import PolicyEngine
 from ..optim import FusedAdam
-from ..parallel import StageAllReducer
+from ..parallel import StageAllReducer, stage_ranges
 
 CAMERA = dict(w=384.0, h=160.0, fov=90.0, world_y=1.4, fixed_offset=4.0, pixels_per_meter=5.0, crop_size=192.0)
 
@@ -40,12 +40,31 @@ class NativeTrainer:
     so every rank derives the same coefficient, bit for bit, with no extra collective.  The gradient buffer is not written: `eng.grad_views`
     keep the UNCLIPPED values.  `grad_stats()` -> {"grad_norm", "clip_coef", "clipped_total"} reads the device record (a sync).
 
+    accumulate=K (default 1: exactly the path above, nothing allocated, nothing launched): gradient accumulation over K micro-batches,
+    what K calls of loss.backward() before one optimizer.step() would do in the reference loop.  Every `step(update=True)` is one
+    micro-step of a window of K: its loss gradient is scaled by 1 / (n * world * K), and right behind every backward stage that stage's
+    range of the gradient buffer is added into `accum_flat` (csrc/grad_accum.hip; the first micro-step of a window stores instead of
+    adding and never reads the buffer).  Only the LAST micro-step launches the stage all-reduces -- over the accumulation buffer, still
+    overlapped with the rest of that backward -- and runs the optimizer: K micro-batches cost one set of six bucket all-reduces and one
+    Adam launch chain.  The optimizer and the reducer are built over `accum_flat` / `accum_views` (the layout of `eng.grad_flat` /
+    `eng.grad_views`, pads included), so guard and clipping need no new pass: a NaN or an infinity of any micro-batch survives the sum and
+    the scan of the accumulated buffer skips the whole update; `grad_norm` and `clip_coef` are those of the ACCUMULATED gradient.
+    `eng.grad_views` keep the last micro-batch's values (scaled by 1 / K, and, as above, unclipped).  BatchNorm normalises every
+    micro-batch with its own statistics and advances its running statistics K times per update (as torch does): K x batch is the
+    optimizer's batch, not BatchNorm's.  `accum_index` (0 .. K - 1) is the position of the next micro-step; `reset_accumulation()`
+    abandons an open window; `step(update=False)` never touches the window.
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
-                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False, max_grad_norm=None):
+                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False, max_grad_norm=None, accumulate=1):
         self.student, self.teacher, self.phase, self.batch, self.world = student, teacher, phase, batch, world_size
         self.device = device
+        if int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError("NativeTrainer: accumulate must be a positive integer, got %r" % (accumulate,))
+        self.accumulate = int(accumulate)
+        self.accum_index = 0
+        self.accum_flat, self.accum_views = None, None
         student.train()
         self.eng = student.engine((batch,) + tuple(image_shape), device, max_batch=batch, with_grads=True)
         self.teng = None
@@ -59,9 +78,17 @@ class NativeTrainer:
         self.cam = camera or camera_struct()
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = bool(skip_nonfinite) or max_grad_norm is not None
-        self.opt = FusedAdam(list(student.named_parameters()), self.eng.grad_views, lr=lr, guarded=self.skip_nonfinite,
+        grad_flat, grad_views = self.eng.grad_flat, self.eng.grad_views
+        if self.accumulate > 1:
+            # the sum of a window's micro-batch gradients: the layout of the executor's flat gradient buffer (pads included, zero like
+            # its own), the same strided views; optimizer and reducer read THIS buffer
+            self.accum_flat = torch.zeros_like(self.eng.grad_flat)
+            self.accum_views = {n: torch.as_strided(self.accum_flat, g.shape, g.stride(), g.storage_offset()) for n, g in self.eng.grad_views.items()}
+            self._accum_ranges = stage_ranges(self.eng.grad_spans)
+            grad_flat, grad_views = self.accum_flat, self.accum_views
+        self.opt = FusedAdam(list(student.named_parameters()), grad_views, lr=lr, guarded=self.skip_nonfinite,
                              max_grad_norm=max_grad_norm)
-        self.reducer = StageAllReducer(self.eng.grad_flat, self.eng.grad_spans, group, grad_dtype=grad_dtype)   # grad_dtype: see parallel.py
+        self.reducer = StageAllReducer(grad_flat, self.eng.grad_spans, group, grad_dtype=grad_dtype)   # grad_dtype: see parallel.py
         self.sync_bn = bool(sync_bn and world_size > 1)
         if sync_bn and world_size > 1:
             # BatchNorm over the global batch (not in the reference: it trains 256 images on one device, which is what this
@@ -88,7 +115,7 @@ class NativeTrainer:
     def _loss(self, kind, pred, target, rows, dpred):
         n = pred.shape[0]
         _lib.check(_lib.get().lbc_loss(kind, ctypes.byref(self.cam), _lib.ptr(pred), _lib.ptr(target), n, rows,
-                                       1.0 / (n * self.world), _lib.ptr(self.loss), _lib.ptr(dpred), _lib.stream_for(pred)), "loss")
+                                       1.0 / (n * self.world * self.accumulate), _lib.ptr(self.loss), _lib.ptr(dpred), _lib.stream_for(pred)), "loss")
 
     def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None):
         """x: student input, float32 (N,C,H,W) in [0,1] or the dataset's uint8 (N,H,W,C) frames; command one-hot (N,4);
@@ -136,7 +163,9 @@ class NativeTrainer:
             self._loss(3, p_all, target, 20, self.dpred_all); d_all = self.dpred_all[:n]
         else:
             raise ValueError(self.phase)
-        if update:
+        if update and self.accumulate > 1:
+            self._accumulating_backward(d_sel, d_all)
+        elif update:
             for st in range(self.nstages):
                 self.eng.backward(d_sel, d_all, st)
                 self.reducer.launch(st)
@@ -149,6 +178,34 @@ class NativeTrainer:
             self.reducer.wait()
             self.opt.step()
         return self.loss[:n]
+
+    def _accumulating_backward(self, d_sel, d_all):
+        """micro-step `accum_index` of a window of `accumulate`: every backward stage is followed by the accumulation of its range; the
+        last micro-step also launches the stage's bucket (over the accumulation buffer) behind it, then waits and runs the optimizer"""
+        lib, first, last = _lib.get(), int(self.accum_index == 0), self.accum_index == self.accumulate - 1
+        g, acc = self.eng.grad_flat, self.accum_flat
+        for st in range(self.nstages):
+            self.eng.backward(d_sel, d_all, st)
+            lo, hi = self._accum_ranges[st]
+            _lib.check(lib.lbc_grad_accumulate(ctypes.c_void_p(g.data_ptr() + 4 * lo), ctypes.c_void_p(acc.data_ptr() + 4 * lo), hi - lo, first,
+                                               _lib.stream_for(g)), "grad_accumulate")
+            if last:
+                self.reducer.launch(st)
+                if self.sync_bn:
+                    self.reducer.fence()        # (the one-order rule between the two communicators: see step())
+        if last:
+            self.reducer.wait()
+            self.opt.step()
+            self.accum_index = 0
+        else:
+            self.accum_index += 1
+
+    def reset_accumulation(self):
+        """abandon an open window (the end of an epoch, a loader that ran dry): -> the number of micro-batches dropped.  Nothing is
+        launched: the next window's first micro-step overwrites the accumulation buffer without reading it.  Parameters, moments and
+        the optimizer's counters are untouched; the BatchNorm running statistics keep what the dropped forwards wrote."""
+        dropped, self.accum_index = self.accum_index, 0
+        return dropped
 
     # ---- resumable state ---------------------------------------------------------------------
     def skipped(self):
@@ -163,19 +220,24 @@ class NativeTrainer:
     def state_dict(self):
         """student state_dict (parameters + BatchNorm buffers, CPU copies), the optimizer in torch.optim.Adam's format, the guard's
         counters (with the number of clipped steps), and what the state was produced under (phase, parameter layout, precision, world
-        size).  The frozen teacher is not part of it: the scripts load it from its own checkpoint.  Syncs the device."""
+        size, micro-batches per update).  The frozen teacher is not part of it: the scripts load it from its own checkpoint.  Syncs the
+        device.  A half-summed accumulation window is not part of the state: inside an open window (accum_index != 0) this raises
+        RuntimeError -- save at a window boundary, or call reset_accumulation() first."""
+        if self.accum_index != 0:
+            raise RuntimeError("NativeTrainer.state_dict: an accumulation window is open (%d of %d micro-batches summed); save at a window "
+                               "boundary or call reset_accumulation() first" % (self.accum_index, self.accumulate))
         total, row = self.opt.skipped()
         return {"format": 1, "phase": self.phase, "precision": getattr(self.student, "precision", "fp32"), "world_size": int(self.world),
-                "layout": self._layout(),
+                "accumulate": int(self.accumulate), "layout": self._layout(),
                 "student": {k: v.detach().cpu().clone() for k, v in self.student.state_dict().items()},
                 "optimizer": self.opt.state_dict(),
                 "guard": {"enabled": self.skip_nonfinite, "skipped_total": total, "skipped_in_a_row": row,
                           "clipped_total": self.opt.grad_stats()["clipped_total"]}}
 
     def load_state_dict(self, sd):
-        """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size or precision
-        and says so (returned notes, also logged).  The guard setting need not match: counters are restored where this trainer has
-        them.  Parameters and buffers are written in place, and the engine derives its weight copies (bf16 / split planes, folded
+        """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size, precision
+        or number of micro-batches per update and says so (returned notes, also logged).  The guard setting need not match: counters are
+        restored where this trainer has them.  Parameters and buffers are written in place, and the engine derives its weight copies (bf16 / split planes, folded
         BatchNorm) again."""
         import logging
         if sd.get("format") != 1:
@@ -190,8 +252,11 @@ class NativeTrainer:
             notes.append("state saved under world size %d, continuing under %d" % (sd["world_size"], self.world))
         if sd["precision"] != getattr(self.student, "precision", "fp32"):
             notes.append("state saved in precision %s, continuing in %s" % (sd["precision"], getattr(self.student, "precision", "fp32")))
+        if int(sd.get("accumulate", 1)) != self.accumulate:      # (a state from before the field: one micro-batch per update)
+            notes.append("state saved with %d micro-batches per update, continuing with %d" % (sd.get("accumulate", 1), self.accumulate))
         for n in notes:
             logging.getLogger(__name__).warning("NativeTrainer.load_state_dict: %s", n)
+        self.accum_index = 0             # (a state is always taken at a window boundary; whatever window was open here is abandoned)
         self.student.load_state_dict(sd["student"])
         self.opt.load_state_dict(sd["optimizer"])
         g = sd.get("guard") or {}

@@ -1,4 +1,4 @@
-"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm.
+"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -27,6 +27,48 @@ def add_arguments(parser, with_resume=True):
     parser.add_argument("--max-skipped", type=int, default=50,
                         help="with --skip-nonfinite: abort when more steps than this were skipped in a row (checked on logging iterations)")
     add_clip_arguments(parser)
+    add_accumulate_argument(parser)
+
+
+def add_accumulate_argument(parser):
+    parser.add_argument("--accumulate", type=int, default=1, metavar="K",
+                        help="sum the gradients of K loader iterations (micro-batches) on the device before every optimizer step: "
+                             "K x batch_size is the optimizer's batch; BatchNorm still normalises each micro-batch on its own.  Default 1: off")
+
+
+def accumulate_entries(parsed):
+    """config entry of --accumulate; a run without it writes the config.json it always wrote"""
+    if parsed.accumulate < 1:
+        raise SystemExit("--accumulate needs a positive number of micro-batches")
+    return {"accumulate": int(parsed.accumulate)} if parsed.accumulate != 1 else {}
+
+
+class Windows:
+    """what a training pass of a run with --accumulate K counts: loader iterations go on counting as they always did, `optimizer_steps`
+    counts the windows of K micro-batches this pass has closed (each one update, applied or skipped by the guard).  Without the flag
+    every method does nothing and logs nothing."""
+
+    def __init__(self, config, trainer, first_iteration=0):
+        self.k, self.trainer = int(config.get("accumulate", 1)), trainer
+        self.optimizer_steps = int(first_iteration) // self.k      # (a pass continued from a state: states are written at boundaries)
+
+    def after_step(self, updated):
+        """call after every trainer.step of the pass; updated: the step ran with update=True"""
+        if self.k > 1 and updated and self.trainer.accum_index == 0:
+            self.optimizer_steps += 1
+
+    def log(self, log_scalar, **tags):
+        if self.k > 1:
+            log_scalar(optimizer_steps=self.optimizer_steps, **tags)
+
+    def end_pass(self, log_scalar, **tags):
+        """the end of an epoch: an incomplete window is discarded (the epoch-end state is then always at a window boundary) and the
+        number of micro-batches it held is logged as dropped_micro_batches.  -> that number"""
+        if self.k <= 1:
+            return 0
+        dropped = self.trainer.reset_accumulation()
+        log_scalar(dropped_micro_batches=dropped, **tags)
+        return dropped
 
 
 def add_clip_arguments(parser):
@@ -72,6 +114,7 @@ def config_entries(parsed):
     if parsed.skip_nonfinite:
         out.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
     out.update(clip_entries(parsed))
+    out.update(accumulate_entries(parsed))
     return out
 
 
@@ -141,9 +184,11 @@ def load(config, trainer, loaders):
 
 
 def maybe_save_inside_epoch(config, trainer, loaders, epoch, iteration):
-    """--save_state_every N: after training iteration `iteration` (1-based) of epoch `epoch`"""
+    """--save_state_every N: after training iteration `iteration` (1-based) of epoch `epoch`.  With --accumulate K a state is only
+    written at a window boundary (NativeTrainer.state_dict refuses an open window): the first boundary at or after every multiple of N."""
     n = config.get("save_state_every", 0)
-    if n > 0 and iteration % n == 0:
+    k = int(config.get("accumulate", 1))
+    if n > 0 and trainer.accum_index == 0 and iteration // n > (iteration - k) // n:
         save(config, trainer, loaders, epoch - 1)
 
 

@@ -26,11 +26,16 @@ SAVE_EPOCHS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1000]
 def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
     """reference train_birdview.py:102-153"""
     tick = time.time()
+    update = is_train and not is_first_epoch
+    windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
-        loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=is_train and not is_first_epoch, train_mode=is_train)
+        loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=update, train_mode=is_train)
+        windows.after_step(update)
         if (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
+            if update:
+                windows.log(bzu.log.scalar, is_train=is_train)
             skipped = resume.check_skipped(config, trainer, "train_birdview") if is_train else None
             if skipped is not None:
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
@@ -43,6 +48,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
+    if update:
+        windows.end_pass(bzu.log.scalar, is_train=is_train)
 
 
 def train(config):
@@ -62,7 +69,7 @@ def train(config):
     data_train, data_val = make_loaders(config, device, rank, world)
     trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world,
                             skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
     loaders = {"train": data_train, "val": data_val}
     # --resume: the full state (train_state.th: optimizer, loaders, RNG, epoch) when there is one; without it, as before, the newest
     # model-%d.th with a fresh Adam from epoch 0

@@ -32,11 +32,16 @@ SAVE_EPOCHS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1000]
 def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
     """reference train_image_phase0.py:152-209"""
     tick = time.time()
+    update = is_train and not is_first_epoch
+    windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
-        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=is_train and not is_first_epoch, train_mode=is_train)
+        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train)
+        windows.after_step(update)
         if (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
+            if update:
+                windows.log(bzu.log.scalar, is_train=is_train)
             skipped = resume.check_skipped(config, trainer, "phase 0") if is_train else None
             if skipped is not None:
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
@@ -49,6 +54,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
+    if update:
+        windows.end_pass(bzu.log.scalar, is_train=is_train)
 
 
 def train(config):
@@ -71,7 +78,7 @@ def train(config):
     cam = camera_struct(**{k: float(v) for k, v in config["camera_args"].items()})
     trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
                             skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
     loaders = {"train": data_train, "val": data_val}
     state = resume.load(config, trainer, loaders)
     for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):

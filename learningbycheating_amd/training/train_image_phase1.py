@@ -61,12 +61,15 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
     """reference train_image_phase1.py:157-229; epoch 0 is the reference's 11-iteration dry run without updates"""
     tick = time.time()
     device = config["device"]
+    update = is_train and not is_first_epoch
+    windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
     # (a loader restored in the middle of its pass hands out the rest of it: the iteration count goes on where it stood)
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(device)
         if is_train and config["speed_noise"] > 0:
             speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
-        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=is_train and not is_first_epoch, train_mode=is_train)
+        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train)
+        windows.after_step(update)
         should_log = (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch
         if should_log:
             lm = loss.mean().item()          # device->host sync only when logging, as the reference (:207-221)
@@ -79,6 +82,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
                 raise FloatingPointError("phase-1 loss is %s: a predicted waypoint reached the horizon (1/y pole of the "
                                          "unprojection); start from a phase-0 checkpoint" % lm)
             bzu.log.scalar(is_train=is_train, loss_mean=lm)
+            if update:
+                windows.log(bzu.log.scalar, is_train=is_train)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9), images_per_sec=rgb_image.shape[0] * config["world_size"] / max(now - tick, 1e-9))
         tick = now
@@ -86,6 +91,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
         if is_first_epoch and i == 10:
             break
+    if update:
+        windows.end_pass(bzu.log.scalar, is_train=is_train)
 
 
 def train(config):
@@ -111,7 +118,7 @@ def train(config):
     cam = camera_struct(**{k: float(v) for k, v in config["agent_args"]["camera_args"].items()})
     trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=1, lr=config["optimizer_args"]["lr"],
                             world_size=world, camera=cam, skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
     loaders = {"train": data_train, "val": data_val}
     state = resume.load(config, trainer, loaders)
     for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):

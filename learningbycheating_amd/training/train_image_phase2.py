@@ -50,7 +50,9 @@ def _fresh_optimizer(trainer, config, lr):
     """fresh moments each epoch, as the reference re-creates its Adam there.  With --clip-grad-norm / --log-grad-norm the number of
     clipped steps goes on counting across the epochs of a run (read and written at the epoch boundary, where the loop syncs anyway)."""
     clipped = trainer.opt.grad_stats()["clipped_total"]
-    trainer.opt = FusedAdam(list(trainer.student.named_parameters()), trainer.eng.grad_views, lr=lr,
+    # (--accumulate: the optimizer reads the accumulation buffer; the loop closes every epoch at a window boundary)
+    grads = trainer.accum_views if trainer.accum_views is not None else trainer.eng.grad_views
+    trainer.opt = FusedAdam(list(trainer.student.named_parameters()), grads, lr=lr,
                             guarded=config.get("skip_nonfinite", False), max_grad_norm=config.get("max_grad_norm"))
     trainer.opt.set_clipped(clipped)
 
@@ -74,6 +76,7 @@ def _train(replay_buffer, trainer, config, episode):
         _fresh_optimizer(trainer, config, 1e-4)
         net.train()
         replay_buffer.init_new_weights()
+        windows = resume.Windows(config, trainer)
         for i in range(len(replay_buffer) // bs):                                              # drop_last=True
             idx = replay_buffer.sample_indices(bs)
             rgb, bv, cmd, speed = replay_buffer.batch(idx)
@@ -81,10 +84,13 @@ def _train(replay_buffer, trainer, config, episode):
             if config["speed_noise"] > 0:
                 speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
             loss = trainer.step(rgb, speed, command, birdview=bv)
+            windows.after_step(True)
             replay_buffer.update_weights(idx, phase2_weights(trainer, trainer.last_pred[0], trainer.last_teacher[0]))
             if i % int(config["log_iterations"]) == 0:
                 bzu.log.scalar(loss_mean=loss.mean().item())
+                windows.log(bzu.log.scalar)
                 _log_guard(trainer, config)
+        windows.end_pass(bzu.log.scalar)
         replay_buffer.normalize_weights()
         # the reference evaluates (eval mode) and visualises the 32 highest-weight samples here (:229-250); visualisation
         # is outside the hot path, the forward is kept so that the same kernels run
@@ -217,11 +223,15 @@ def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start
         _fresh_optimizer(trainer, config, config.get("lr", 1e-4))
         net.train()
         replay_buffer.init_new_weights()
+        windows = resume.Windows(config, trainer)
         for i in range(len(replay_buffer) // bs):                                              # drop_last=True
             _, loss = _device_step(replay_buffer, trainer, config, augmenter)
+            windows.after_step(True)
             if i % int(config["log_iterations"]) == 0:
                 bzu.log.scalar(loss_mean=loss.mean().item())
+                windows.log(bzu.log.scalar)
                 _log_guard(trainer, config)
+        windows.end_pass(bzu.log.scalar)
         replay_buffer.normalize_weights()                                                      # (the epoch's one read-back)
         # the reference's eval-mode forward over the highest-weight samples (:229-250), on the trainer's own executor
         top, rgb, bv, command, speed = replay_buffer.get_highest_k(min(32, len(replay_buffer), trainer.batch))
@@ -256,6 +266,7 @@ def main(argv=None, on_epoch_end=None):
                         help="skip (on the device) every optimizer step whose gradients hold a NaN or an infinity")
     parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
     resume.add_clip_arguments(parser)
+    resume.add_accumulate_argument(parser)
     parser.add_argument("--replay", choices=["host", "device"], default="host",
                         help="host = the replay buffer samples on the host and builds float batches; device = buffer, weighted sampling, uint8 gather "
                              "and weight write-back on the GPU, no host round trip inside a step")
@@ -291,6 +302,7 @@ def main(argv=None, on_epoch_end=None):
     if parsed.skip_nonfinite:
         config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
     config.update(resume.clip_entries(parsed))
+    config.update(resume.accumulate_entries(parsed))
     if device_replay:
         config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
                       world_size=world, synthetic_frames=True)
@@ -314,7 +326,7 @@ def main(argv=None, on_epoch_end=None):
     broadcast_module(teacher)
     trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
                             camera=camera_struct(), skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
     if device_replay:
         buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
