@@ -35,7 +35,9 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      guarded step finds out with dlsym (the Python binding fails on the missing symbol when it declares its signatures).
  *      Later again, the same way: lbc_adam_clip_state, lbc_adam_clip_state_bytes, lbc_adam_step_clipped (a new record type and
  *      new exports; lbc_adam_state and the guarded step are unchanged).  And once more: lbc_grad_accumulate (one new export, no
- *      record, nothing existing changed).
+ *      record, nothing existing changed).  And again: lbc_adam_recipe, lbc_adam_recipe_state, lbc_adam_recipe_state_bytes,
+ *      lbc_adam_step_recipe (a new descriptor, a new record type that starts with lbc_adam_clip_state's 64 bytes, new exports; the
+ *      three existing steps and their records are unchanged).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -287,6 +289,70 @@ typedef struct lbc_adam_clip_state {
 size_t lbc_adam_clip_state_bytes(int nchunks);
 int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double lr, double beta1, double beta2,
                           double eps, double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, lbc_stream_t stream);
+
+/* The training recipe on top of the clipped step: a learning-rate schedule evaluated on the device from the record's own step
+ * count, decoupled weight decay (torch.optim.AdamW) and an exponential moving average of the parameters, in one step of three
+ * launches like lbc_adam_step_clipped (norm pass, one bookkeeping launch, one update launch), again without a device-to-host
+ * copy or a synchronisation.  The reference trains with a constant rate, no decay and no average.
+ * The recipe is a host struct, read during the call only.  Start it as `lbc_adam_recipe r = LBC_ADAM_RECIPE_INIT;` -- struct_size is
+ * checked like lbc_conv_desc's.  On a clean step the bookkeeping thread computes, in double, from k = step - 1 (the number of
+ * updates applied before this one; a skipped step does not advance it):
+ *     k < warmup_steps:   lr = base_lr * (warmup_start + (1 - warmup_start) * k / warmup_steps)
+ *     else, j = k - warmup_steps:
+ *       LBC_LR_CONSTANT   lr = base_lr
+ *       LBC_LR_COSINE     lr = min_lr + (base_lr - min_lr) * 0.5 * (1 + cos(pi * min(j, T - W) / (T - W))),  T = total_steps, W = warmup_steps
+ *       LBC_LR_STEP       lr = base_lr * gamma^floor(j / step_size)
+ * lr_over_bc1 = (float)(lr / (1 - beta1^step)); decay_factor = decoupled ? (float)(1 - lr * weight_decay) : 1; ema_updates += 1 when
+ * ema_decay > 0.  A skipped step keeps lr, decay_factor and ema_updates, as it keeps grad_norm.
+ * The update is that of lbc_adam_step_clipped (same roundings: a recipe with a constant rate, no warm-up, coupled decay and no
+ * average IS that step, bit for bit) with two additions.  decoupled != 0: p is first multiplied by decay_factor, the product rounded
+ * to f32 on its own, and the coupled term is dropped.  ema_decay > 0: e = e + (float)(1 - ema_decay) * (p' - e) on the updated p'.
+ * ema_dev is a device array of one float* per chunk: the chunk's slice of the shadow, in the element order and padding of m and v
+ * (16-byte aligned like them); NULL when ema_decay == 0.  A skipped step returns before it loads anything: e keeps its bits too.
+ * The record is lbc_adam_recipe_state_bytes(nchunks) bytes: the header below and one double per chunk; the contract of
+ * lbc_adam_clip_state (zero-filled once, 8-byte aligned, counters uploaded to resume -- ema_updates with them).
+ * Refused with LBC_EINVAL: a null recipe / state / table, a bad struct_size, a misaligned state, nchunks <= 0, an unknown schedule,
+ * any NaN, base_lr < 0, warmup_steps < 0, warmup_start outside [0, 1], cosine with total_steps <= warmup_steps, step with
+ * step_size < 1 or gamma <= 0, ema_decay outside [0, 1), ema_decay > 0 with ema_dev NULL, decoupled with weight_decay < 0. */
+enum { LBC_LR_CONSTANT = 0, LBC_LR_COSINE = 1, LBC_LR_STEP = 2 };
+typedef struct lbc_adam_recipe {
+    unsigned struct_size;        /* = sizeof(lbc_adam_recipe) */
+    int schedule;                /* LBC_LR_* */
+    double base_lr;
+    long long warmup_steps;      /* W: optimizer steps of linear warm-up; 0 = none */
+    double warmup_start;         /* s0: the first step's fraction of base_lr */
+    long long total_steps;       /* T (cosine): the rate reaches min_lr at step T and stays there */
+    double min_lr;               /* (cosine) */
+    long long step_size;         /* S (step) */
+    double gamma;                /* (step) */
+    double weight_decay;
+    int decoupled;               /* 0: the coupled L2 term of lbc_adam_step; 1: AdamW */
+    int reserved;                /* zero */
+    double max_norm;             /* as lbc_adam_step_clipped: <= 0 measures the norm without clipping */
+    double ema_decay;            /* 0 = no average; else in (0, 1) */
+    double beta1, beta2, eps;
+} lbc_adam_recipe;
+#define LBC_ADAM_RECIPE_INIT { (unsigned)sizeof(lbc_adam_recipe), 0, 0.0, 0, 0.0, 0, 0.0, 1, 1.0, 0.0, 0, 0, 0.0, 0.0, 0.9, 0.999, 1e-8 }
+typedef struct lbc_adam_recipe_state {
+    long long step;              /* the 64 bytes of lbc_adam_clip_state, same meaning and offsets */
+    long long skipped_total;
+    long long skipped_in_a_row;
+    int bad;
+    int scan_flag;
+    float lr_over_bc1;
+    float inv_bc2_sqrt;
+    double grad_norm;
+    float clip_coef;
+    int reserved;
+    long long clipped_total;
+    double lr;                   /* the schedule's rate of the last clean step */
+    float decay_factor;          /* what that step multiplied p by in front of the update; 1 without decoupled decay */
+    int reserved2;               /* zero */
+    long long ema_updates;       /* applied steps that moved the average since the record was zeroed */
+} lbc_adam_recipe_state;
+size_t lbc_adam_recipe_state_bytes(int nchunks);
+int lbc_adam_step_recipe(const lbc_adam_chunk* chunks_dev, int nchunks, const lbc_adam_recipe* recipe, float* const* ema_dev,
+                         lbc_adam_recipe_state* state_dev, lbc_stream_t stream);
 
 /* Gradient accumulation over micro-batches (what the reference would get from calling loss.backward() K times before
  * optimizer.step(); it never does): lbc_net_backward overwrites the bound gradients, so a caller that wants the sum of K backward

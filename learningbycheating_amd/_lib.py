@@ -64,6 +64,30 @@ class AdamClipState(ctypes.Structure):
                                      ("clipped_total", ctypes.c_longlong)]
 
 
+class AdamRecipeState(ctypes.Structure):
+    """lbc_adam_recipe_state: the header of the recipe step's device record (lbc_adam_clip_state's 64 bytes, then the schedule's rate, the
+    decoupled decay factor and the number of moving-average updates); one double per chunk follows it on the device"""
+    _fields_ = AdamClipState._fields_ + [("lr", ctypes.c_double), ("decay_factor", c_float), ("reserved2", c_int),
+                                         ("ema_updates", ctypes.c_longlong)]
+
+
+LR_SCHEDULES = {"constant": 0, "cosine": 1, "step": 2}      # LBC_LR_*
+
+
+class AdamRecipe(ctypes.Structure):
+    """lbc_adam_recipe (a host struct, read during the call); struct_size is filled in here and the defaults are LBC_ADAM_RECIPE_INIT's"""
+    _fields_ = [("struct_size", ctypes.c_uint), ("schedule", c_int), ("base_lr", ctypes.c_double), ("warmup_steps", ctypes.c_longlong),
+                ("warmup_start", ctypes.c_double), ("total_steps", ctypes.c_longlong), ("min_lr", ctypes.c_double),
+                ("step_size", ctypes.c_longlong), ("gamma", ctypes.c_double), ("weight_decay", ctypes.c_double), ("decoupled", c_int),
+                ("reserved", c_int), ("max_norm", ctypes.c_double), ("ema_decay", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+    def __init__(self, **kw):
+        d = dict(struct_size=ctypes.sizeof(AdamRecipe), step_size=1, gamma=1.0, beta1=0.9, beta2=0.999, eps=1e-8)
+        d.update(kw)
+        super().__init__(**d)
+
+
 _SIGNATURES = {
     "lbc_last_error": (c_char_p, []),
     "lbc_backend": (c_char_p, []),
@@ -107,6 +131,8 @@ _SIGNATURES = {
     "lbc_adam_step_guarded": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 5 + [c_void_p, c_void_p]),
     "lbc_adam_clip_state_bytes": (c_size_t, [c_int]),
     "lbc_adam_step_clipped": (c_int, [c_void_p, c_int] + [ctypes.c_double] * 6 + [c_void_p, c_void_p]),
+    "lbc_adam_recipe_state_bytes": (c_size_t, [c_int]),
+    "lbc_adam_step_recipe": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lbc_grad_accumulate": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
     "lbc_bn_stats": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "lbc_bn_finalize_stats": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 5),

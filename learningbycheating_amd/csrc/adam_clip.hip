@@ -19,6 +19,7 @@
 #include "lbc_common.hpp"
 #include "lbc_hip.h"
 #include "lbc_kernels.hpp"
+#include "adam_update.hpp"      // clipped_update<kTail>: one element of the update, shared with adam_recipe.hip
 
 namespace {
 
@@ -125,45 +126,6 @@ __global__ __launch_bounds__(256) void adam_clip_book_k(lbc_adam_clip_state* __r
     st->clipped_total += (coef < 1.0f) ? 1 : 0;
 }
 
-// One element of the update.  The contract with adam_guarded_k is bitwise, and that kernel leaves the choice of which multiply fuses
-// into which add to the compiler (-ffp-contract=fast), and a second copy of its expressions behind a product by the coefficient is
-// not guaranteed the same choices.  So on the device nothing here is left to the compiler: contraction is off for the whole function
-// and every fused operation is written out, mirroring what hipcc emits for adam_guarded_k (read from its gfx950 ISA as compiled by
-// ROCm 7.2.0):
-//     gg = fma(wd, p, g)        m' = fma(omb1, gg - m, m)        denom = fma(inv_bc2_sqrt, sqrt(v'), eps)        p' = fma(-lr, m' / denom, p)
-//     16-byte loop:  v' = fma(gg, omb2 * gg, beta2 * v)          scalar tail:  v' = beta2 * v + (omb2 * gg) * gg   (two roundings)
-// with g = g * coef rounded on its own in front.  THIS LIST DEPENDS ON THE COMPILER: a hipcc that fuses adam_guarded_k differently
-// breaks the bitwise contract.  tests/test_grad_clip.py compares the two kernels bit for bit on the GPU with and without weight
-// decay and fails then; the list is read off adam_guarded_k's ISA again (kTail separates the two loops because they differ today).
-// The emulated build fuses nothing (x86-64 baseline has no fma): there the expressions of adam_guarded_k are kept as they are, with
-// only the product by the coefficient kept from contracting.
-template <bool kTail>
-__device__ __forceinline__ void clipped_update(float& p, float g, float& m, float& v, float coef, float wd, float beta2, float omb1,
-                                               float omb2, float eps, float lr_over_bc1, float inv_bc2_sqrt)
-{
-#ifdef LBC_HIP_EMULATED_FOR_TESTS
-    float gs;
-    {
-#pragma clang fp contract(off)
-        gs = g * coef;
-    }
-    const float gg = gs + wd * p;
-    m = m + (gg - m) * omb1;
-    v = beta2 * v + omb2 * gg * gg;
-    const float denom = sqrtf(v) * inv_bc2_sqrt + eps;
-    p = p - lr_over_bc1 * (m / denom);
-#else
-#pragma clang fp contract(off)
-    const float gs = g * coef;
-    const float gg = __builtin_fmaf(wd, p, gs);
-    m = __builtin_fmaf(omb1, gg - m, m);
-    const float t = omb2 * gg, bv = beta2 * v;
-    v = kTail ? bv + t * gg : __builtin_fmaf(gg, t, bv);
-    const float denom = __builtin_fmaf(inv_bc2_sqrt, sqrtf(v), eps);
-    p = __builtin_fmaf(-lr_over_bc1, m / denom, p);
-#endif
-}
-
 __global__ __launch_bounds__(256) void adam_clipped_k(const AdamChunk* __restrict__ chunks, const lbc_adam_clip_state* __restrict__ st,
                                                       float beta1, float beta2, float omb1, float omb2, float eps, float wd)
 {
@@ -208,4 +170,10 @@ int lbc_adam_clipped_launch(const AdamChunk* chunks_dev, int nchunks, double lr,
     hipLaunchKernelGGL(adam_clipped_k, dim3((unsigned)nchunks), dim3(256), 0, s, chunks_dev, (const lbc_adam_clip_state*)state_dev,
                        (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay);
     return lbc_check_launch("adam_clipped");
+}
+
+// the norm pass alone, for adam_recipe.hip: its record starts with the 64 bytes of lbc_adam_clip_state (the pass writes scan_flag only)
+void lbc_adam_norm_pass(const AdamChunk* chunks_dev, int nchunks, lbc_adam_clip_state* state_dev, double* partial, hipStream_t s)
+{
+    hipLaunchKernelGGL(adam_norm_k, dim3((unsigned)nchunks), dim3(256), 0, s, chunks_dev, state_dev, partial);
 }

@@ -39,6 +39,18 @@ int lbc_adam_step_clipped(const lbc_adam_chunk* chunks_dev, int nchunks, double 
                                    max_norm, state_dev, (hipStream_t)stream);
 }
 
+size_t lbc_adam_recipe_state_bytes(int nchunks) { return sizeof(lbc_adam_recipe_state) + sizeof(double) * (size_t)(nchunks > 0 ? nchunks : 0); }
+
+int lbc_adam_step_recipe(const lbc_adam_chunk* chunks_dev, int nchunks, const lbc_adam_recipe* recipe, float* const* ema_dev,
+                         lbc_adam_recipe_state* state_dev, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_adam_recipe_state) == 88 && offsetof(lbc_adam_recipe_state, lr) == sizeof(lbc_adam_clip_state) &&
+                  offsetof(lbc_adam_recipe_state, clipped_total) == offsetof(lbc_adam_clip_state, clipped_total) &&
+                  offsetof(lbc_adam_recipe_state, decay_factor) == 72 && offsetof(lbc_adam_recipe_state, ema_updates) == 80,
+                  "lbc_adam_recipe_state layout (include/lbc_hip.h)");
+    return lbc_adam_recipe_launch(reinterpret_cast<const AdamChunk*>(chunks_dev), nchunks, recipe, ema_dev, state_dev, (hipStream_t)stream);
+}
+
 int lbc_grad_accumulate(const float* g, float* acc, long long n, int first, lbc_stream_t stream)
 {
     return lbc_grad_accumulate_launch(g, acc, n, first, (hipStream_t)stream);

@@ -276,5 +276,12 @@ int lbc_adam_guarded_launch(const AdamChunk* chunks_dev, int nchunks, double lr,
 struct lbc_adam_clip_state;
 int lbc_adam_clipped_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, hipStream_t s);
+void lbc_adam_norm_pass(const AdamChunk* chunks_dev, int nchunks, lbc_adam_clip_state* state_dev, double* partial, hipStream_t s);   // its first launch alone
+// adam_recipe.hip: the clipped step with a learning-rate schedule evaluated in the bookkeeping thread, decoupled weight decay and an
+// exponential moving average of the parameters (include/lbc_hip.h lbc_adam_recipe / lbc_adam_recipe_state).  The recipe is validated here.
+struct lbc_adam_recipe;
+struct lbc_adam_recipe_state;
+int lbc_adam_recipe_launch(const AdamChunk* chunks_dev, int nchunks, const lbc_adam_recipe* recipe, float* const* ema_dev,
+                           lbc_adam_recipe_state* state_dev, hipStream_t s);
 // grad_accum.hip: acc = first ? g : acc + g over n floats (gradient accumulation over micro-batches); one launch, no atomics
 int lbc_grad_accumulate_launch(const float* g, float* acc, long long n, int first, hipStream_t s);

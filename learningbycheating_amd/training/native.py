@@ -3,13 +3,14 @@
     (+ bucketed RCCL all-reduce) -> fused Adam
 = reference training/train_image_phase1.py:174-205 (phase 1), train_image_phase0.py:163-189
 (phase 0) and train_birdview.py:116-128 (bird-view behaviour cloning)."""
+import contextlib
 import ctypes
 
 import torch
 
 from .. import _lib
 from ..engine import PolicyEngine
-from ..optim import FusedAdam
+from ..optim import FusedAdam, LRSchedule
 from ..parallel import StageAllReducer, stage_ranges
 
 CAMERA = dict(w=384.0, h=160.0, fov=90.0, world_y=1.4, fixed_offset=4.0, pixels_per_meter=5.0, crop_size=192.0)
@@ -54,10 +55,21 @@ class NativeTrainer:
     optimizer's batch, not BatchNorm's.  `accum_index` (0 .. K - 1) is the position of the next micro-step; `reset_accumulation()`
     abandons an open window; `step(update=False)` never touches the window.
 
+    lr_schedule=... / weight_decay=X / ema_decay=D (any of them implies the guard and the norm measurement: FusedAdam's recipe path,
+    csrc/adam_recipe.hip).  lr_schedule (an optim.LRSchedule or a dict of its fields) makes `lr` the base rate of a schedule that the
+    optimizer's bookkeeping thread evaluates at Adam's own step count: a skipped step does not advance it, with accumulate=K it advances
+    once per window, and no step syncs.  weight_decay is DECOUPLED (torch.optim.AdamW; every parameter, BatchNorm and biases included,
+    as AdamW with one group).  ema_decay keeps an exponential moving average of the student's parameters (`opt.ema`), updated inside
+    the optimizer's update launch and left alone by a skipped step; BatchNorm buffers are not averaged.  `lr_stats()` ->
+    {"lr", "ema_updates"} reads the record (a sync); `ema_state_dict()` is the student's state_dict with the averaged parameters;
+    `with trainer.ema_weights():` runs on them.  Under data parallelism the ranks agree bit for bit: lr is a function of the record's
+    step, the average a function of identical updated parameters.
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
-                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False, max_grad_norm=None, accumulate=1):
+                 sync_bn=False, teacher_shape=(7, 192, 192), skip_nonfinite=False, max_grad_norm=None, accumulate=1, lr_schedule=None, weight_decay=0.0,
+                 ema_decay=None):
         self.student, self.teacher, self.phase, self.batch, self.world = student, teacher, phase, batch, world_size
         self.device = device
         if int(accumulate) != accumulate or int(accumulate) < 1:
@@ -77,7 +89,14 @@ class NativeTrainer:
             self._teacher_versions = self._versions(teacher)
         self.cam = camera or camera_struct()
         self.max_grad_norm = max_grad_norm
-        self.skip_nonfinite = bool(skip_nonfinite) or max_grad_norm is not None
+        self.lr_schedule = None if lr_schedule is None else LRSchedule.of(lr_schedule)
+        self.weight_decay = float(weight_decay)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.weight_decay < 0 or self.weight_decay != self.weight_decay:
+            raise ValueError("NativeTrainer: weight_decay must be a non-negative number, got %r" % (weight_decay,))
+        self.recipe = self.lr_schedule is not None or self.weight_decay != 0.0 or self.ema_decay is not None
+        self.skip_nonfinite = bool(skip_nonfinite) or max_grad_norm is not None or self.recipe
+        self._in_ema_weights = False
         grad_flat, grad_views = self.eng.grad_flat, self.eng.grad_views
         if self.accumulate > 1:
             # the sum of a window's micro-batch gradients: the layout of the executor's flat gradient buffer (pads included, zero like
@@ -86,8 +105,12 @@ class NativeTrainer:
             self.accum_views = {n: torch.as_strided(self.accum_flat, g.shape, g.stride(), g.storage_offset()) for n, g in self.eng.grad_views.items()}
             self._accum_ranges = stage_ranges(self.eng.grad_spans)
             grad_flat, grad_views = self.accum_flat, self.accum_views
+        recipe = {}
+        if self.recipe:
+            recipe = dict(schedule=self.lr_schedule or LRSchedule(), weight_decay=self.weight_decay, decoupled_weight_decay=self.weight_decay != 0.0,
+                          ema_decay=self.ema_decay)
         self.opt = FusedAdam(list(student.named_parameters()), grad_views, lr=lr, guarded=self.skip_nonfinite,
-                             max_grad_norm=max_grad_norm)
+                             max_grad_norm=max_grad_norm, **recipe)
         self.reducer = StageAllReducer(grad_flat, self.eng.grad_spans, group, grad_dtype=grad_dtype)   # grad_dtype: see parallel.py
         self.sync_bn = bool(sync_bn and world_size > 1)
         if sync_bn and world_size > 1:
@@ -124,6 +147,8 @@ class NativeTrainer:
         on_forward (parity tests): called with the trainer after the student's forward, before the loss and the backward."""
         if not train_mode and update:
             raise ValueError("an eval-mode step cannot update (backward through running-statistics BatchNorm is not implemented)")
+        if update and self._in_ema_weights:
+            raise RuntimeError("NativeTrainer.step: an updating step inside ema_weights() would train the average")
         n = x.shape[0]
         # the executor takes raw pointers to dense tensors; a permuted / sliced view is packed first (the reference's
         # nn.Module accepts any strides)
@@ -214,6 +239,54 @@ class NativeTrainer:
     def grad_stats(self):
         return self.opt.grad_stats()
 
+    def lr_stats(self):
+        return self.opt.lr_stats()
+
+    # ---- the averaged weights ----------------------------------------------------------------
+    def ema_state_dict(self):
+        """the student's state_dict() (same keys, devices and memory formats, so it loads wherever that does) with every trained parameter
+        replaced by its moving average; BatchNorm buffers and parameters without a gradient are the student's own.  Copies; a sync."""
+        if self.opt.ema is None:
+            raise RuntimeError("NativeTrainer.ema_state_dict: this trainer keeps no average (ema_decay=None)")
+        sd = {k: v.detach().clone() for k, v in self.student.state_dict().items()}
+        for n in self.opt.names:
+            sd[n].copy_(self.opt.ema_of(n))
+        return sd
+
+    def _exchange_ema(self):
+        params = dict(self.student.named_parameters())
+        for n in self.opt.names:
+            p, e = params[n].data, self.opt.ema_of(n)
+            tmp = p.clone()
+            p.copy_(e)
+            e.copy_(tmp)
+        self.eng.invalidate()              # (written through .data: the engine derives its weight copies again)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the block the student's parameters ARE the averaged weights and `opt.ema` holds the trained ones: an exchange in
+        place, nothing allocated beyond one tensor at a time; the engine's derived weight copies are invalidated on entry and on exit.
+        For `step(update=False)` (the validation pass); an updating step inside is refused, and so is opening it inside an accumulation
+        window."""
+        if self.opt.ema is None:
+            raise RuntimeError("NativeTrainer.ema_weights: this trainer keeps no average (ema_decay=None)")
+        if self.accum_index != 0:
+            raise RuntimeError("NativeTrainer.ema_weights: an accumulation window is open (%d of %d micro-batches summed)"
+                               % (self.accum_index, self.accumulate))
+        if self._in_ema_weights:
+            raise RuntimeError("NativeTrainer.ema_weights: already inside")
+        self._exchange_ema()
+        self._in_ema_weights = True
+        try:
+            yield self
+        finally:
+            self._in_ema_weights = False
+            self._exchange_ema()
+
+    def _recipe_entry(self):
+        return {"schedule": None if self.lr_schedule is None else self.lr_schedule.as_dict(), "weight_decay": self.weight_decay,
+                "ema_decay": self.ema_decay}
+
     def _layout(self):
         return [[n, list(p.shape)] for n, p in self.student.named_parameters()]
 
@@ -226,20 +299,33 @@ class NativeTrainer:
         if self.accum_index != 0:
             raise RuntimeError("NativeTrainer.state_dict: an accumulation window is open (%d of %d micro-batches summed); save at a window "
                                "boundary or call reset_accumulation() first" % (self.accum_index, self.accumulate))
+        if self._in_ema_weights:
+            raise RuntimeError("NativeTrainer.state_dict: inside ema_weights() the parameters and the average are exchanged; leave the block first")
         total, row = self.opt.skipped()
-        return {"format": 1, "phase": self.phase, "precision": getattr(self.student, "precision", "fp32"), "world_size": int(self.world),
+        sd = {"format": 1, "phase": self.phase, "precision": getattr(self.student, "precision", "fp32"), "world_size": int(self.world),
                 "accumulate": int(self.accumulate), "layout": self._layout(),
                 "student": {k: v.detach().cpu().clone() for k, v in self.student.state_dict().items()},
                 "optimizer": self.opt.state_dict(),
                 "guard": {"enabled": self.skip_nonfinite, "skipped_total": total, "skipped_in_a_row": row,
                           "clipped_total": self.opt.grad_stats()["clipped_total"]}}
+        if self.recipe:
+            # what the optimizer's torch-format sidecar cannot carry: the schedule, the decay, the average (CPU tensors by parameter name,
+            # logical shapes) and the number of its updates
+            sd["recipe"] = self._recipe_entry()
+            sd["guard"]["ema_updates"] = self.opt.lr_stats()["ema_updates"]
+            if self.opt.ema is not None:
+                sd["ema"] = {n: self.opt.ema_of(n).detach().cpu().clone() for n in self.opt.names}
+        return sd
 
     def load_state_dict(self, sd):
-        """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size, precision
-        or number of micro-batches per update and says so (returned notes, also logged).  The guard setting need not match: counters are
+        """the inverse; refuses a state of another phase or parameter layout (ValueError), accepts another world size, precision,
+        number of micro-batches per update, schedule, weight decay or use of the moving average and says so (returned notes, also logged):
+        schedule, decay and ema_decay are always THIS trainer's arguments, never the state's.  The guard setting need not match: counters are
         restored where this trainer has them.  Parameters and buffers are written in place, and the engine derives its weight copies (bf16 / split planes, folded
         BatchNorm) again."""
         import logging
+        if self._in_ema_weights:
+            raise RuntimeError("NativeTrainer.load_state_dict: inside ema_weights() the parameters and the average are exchanged; leave the block first")
         if sd.get("format") != 1:
             raise ValueError("NativeTrainer.load_state_dict: unknown state format %r" % (sd.get("format"),))
         if sd["phase"] != self.phase:
@@ -254,13 +340,38 @@ class NativeTrainer:
             notes.append("state saved in precision %s, continuing in %s" % (sd["precision"], getattr(self.student, "precision", "fp32")))
         if int(sd.get("accumulate", 1)) != self.accumulate:      # (a state from before the field: one micro-batch per update)
             notes.append("state saved with %d micro-batches per update, continuing with %d" % (sd.get("accumulate", 1), self.accumulate))
+        neutral = {"schedule": None, "weight_decay": 0.0, "ema_decay": None}
+        saved, mine = dict(neutral, **(sd.get("recipe") or {})), self._recipe_entry() if self.recipe else neutral      # (a state from before the field: none of them)
+        if saved["schedule"] != mine["schedule"]:
+            notes.append("state saved under the learning-rate schedule %r, continuing under %r" % (saved["schedule"], mine["schedule"]))
+        # The decay is this trainer's argument, like the schedule: the optimizer group is handed on with THIS trainer's decay, so what the
+        # note says is what the next step does.  What the state trained with is read off its optimizer group, the value the kernel was given
+        group = sd["optimizer"]["param_groups"][0]
+        saved_decay = float(group["weight_decay"]) if group.get("decoupled_weight_decay") else 0.0
+        if saved_decay != mine["weight_decay"]:
+            notes.append("state saved with weight decay %g, continuing with %g" % (saved_decay, mine["weight_decay"]))
+        if (saved["ema_decay"] is None) != (mine["ema_decay"] is None):
+            notes.append("state saved without a moving average of the weights: it starts here as a copy of the restored parameters"
+                         if saved["ema_decay"] is None else "state saved with a moving average of the weights, which this trainer does not keep: dropped")
+        elif saved["ema_decay"] != mine["ema_decay"]:
+            notes.append("state saved with ema_decay %g, continuing with %g" % (saved["ema_decay"], mine["ema_decay"]))
         for n in notes:
             logging.getLogger(__name__).warning("NativeTrainer.load_state_dict: %s", n)
         self.accum_index = 0             # (a state is always taken at a window boundary; whatever window was open here is abandoned)
         self.student.load_state_dict(sd["student"])
-        self.opt.load_state_dict(sd["optimizer"])
+        if self.recipe or group.get("decoupled_weight_decay"):
+            ours = dict(group, weight_decay=self.weight_decay, decoupled_weight_decay=self.opt.decoupled)
+            self.opt.load_state_dict(dict(sd["optimizer"], param_groups=[ours] + list(sd["optimizer"]["param_groups"][1:])))
+        else:
+            self.opt.load_state_dict(sd["optimizer"])       # (neither side knows decoupled decay: the group as it is, as always)
         g = sd.get("guard") or {}
         self.opt.set_skipped(g.get("skipped_total", 0), g.get("skipped_in_a_row", 0))
         self.opt.set_clipped(g.get("clipped_total", 0))
+        if self.opt.ema is not None:
+            params = dict(self.student.named_parameters())
+            kept = sd.get("ema")
+            for n in self.opt.names:
+                self.opt.ema_of(n).copy_(kept[n] if kept is not None else params[n].data)
+            self.opt.set_ema_updates(g.get("ema_updates", 0) if kept is not None else 0)
         self.eng.invalidate()
         return notes

@@ -1,10 +1,12 @@
-"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate.
+"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate /
+--lr-schedule / --weight-decay / --ema-decay.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
 Rank 0 writes it; under WORLD_SIZE > 1 every other rank writes its own loader / RNG part (the loaders are seeded by rank) as
 `train_state.rank%d.th` beside it.  Every file is written to `<name>.tmp` in the same directory and moved into place with
 os.replace: a writer that dies leaves a .tmp nobody reads.  The model-%d.th files are not touched by any of this."""
+import contextlib
 import os
 from pathlib import Path
 
@@ -28,6 +30,95 @@ def add_arguments(parser, with_resume=True):
                         help="with --skip-nonfinite: abort when more steps than this were skipped in a row (checked on logging iterations)")
     add_clip_arguments(parser)
     add_accumulate_argument(parser)
+    add_recipe_arguments(parser)
+
+
+def add_recipe_arguments(parser, per_epoch=False):
+    """per_epoch: the script re-creates its optimizer every epoch (phase 2), and the schedule with it"""
+    again = "  The schedule restarts with the optimizer at every epoch, as Adam's step count does here." if per_epoch else ""
+    parser.add_argument("--lr-schedule", choices=["constant", "cosine", "step"], default=None,
+                        help="learning-rate schedule with --lr as its base rate, evaluated on the device at Adam's own step count (optimizer "
+                             "steps: a skipped step does not advance it, --accumulate K advances it once per K iterations); implies "
+                             "--skip-nonfinite.  Default: the constant --lr." + again)
+    parser.add_argument("--warmup-steps", type=int, default=0, metavar="W", help="linear warm-up over the first W optimizer steps")
+    parser.add_argument("--warmup-start", type=float, default=0.0, metavar="S0", help="the warm-up starts at S0 x --lr (default 0)")
+    parser.add_argument("--lr-total-steps", type=int, default=None, metavar="T",
+                        help="cosine: the rate reaches --lr-min at optimizer step T and stays there (required for cosine)")
+    parser.add_argument("--lr-min", type=float, default=0.0, help="cosine: the final rate")
+    parser.add_argument("--lr-step-size", type=int, default=1, metavar="S", help="step: multiply the rate by --lr-gamma every S optimizer steps")
+    parser.add_argument("--lr-gamma", type=float, default=0.1, help="step: the factor")
+    parser.add_argument("--weight-decay", type=float, default=0.0, metavar="X",
+                        help="decoupled weight decay (torch.optim.AdamW: p *= 1 - lr * X in front of every update, every parameter); "
+                             "implies --skip-nonfinite.  Default 0: off" + again)
+    parser.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                        help="keep an exponential moving average of the weights, e += (1 - D) (p - e) inside every applied optimizer step, "
+                             "and write model-ema-%%d.th beside every model-%%d.th; implies --skip-nonfinite.  Default: off")
+    parser.add_argument("--ema-eval", action="store_true", help="with --ema-decay: run the validation pass on the averaged weights")
+
+
+def recipe_entries(parsed):
+    """config entries of --lr-schedule (and its companions) / --weight-decay / --ema-decay (/ --ema-eval), plus the guard they imply; a run
+    without them writes the config.json it always wrote"""
+    out = {}
+    if parsed.lr_schedule is not None or parsed.warmup_steps:
+        kind = parsed.lr_schedule or "constant"
+        if kind == "cosine" and parsed.lr_total_steps is None:
+            raise SystemExit("--lr-schedule cosine needs --lr-total-steps T (optimizer steps)")
+        if parsed.warmup_steps < 0 or not 0.0 <= parsed.warmup_start <= 1.0:
+            raise SystemExit("--warmup-steps must not be negative and --warmup-start must lie in [0, 1]")
+        sch = {"kind": kind, "warmup_steps": int(parsed.warmup_steps), "warmup_start": float(parsed.warmup_start)}
+        if kind == "cosine":
+            if parsed.lr_total_steps <= parsed.warmup_steps:
+                raise SystemExit("--lr-total-steps must be larger than --warmup-steps")
+            sch.update(total_steps=int(parsed.lr_total_steps), min_lr=float(parsed.lr_min))
+        if kind == "step":
+            if parsed.lr_step_size < 1 or not parsed.lr_gamma > 0:
+                raise SystemExit("--lr-step-size must be at least 1 and --lr-gamma positive")
+            sch.update(step_size=int(parsed.lr_step_size), gamma=float(parsed.lr_gamma))
+        out["lr_schedule"] = sch
+    if parsed.weight_decay:
+        if not parsed.weight_decay > 0:
+            raise SystemExit("--weight-decay must not be negative")
+        out["weight_decay"] = float(parsed.weight_decay)
+    if parsed.ema_decay is not None:
+        if not 0.0 < parsed.ema_decay < 1.0:
+            raise SystemExit("--ema-decay must lie in (0, 1)")
+        out["ema_decay"] = float(parsed.ema_decay)
+        if parsed.ema_eval:
+            out["ema_eval"] = True
+    elif parsed.ema_eval:
+        raise SystemExit("--ema-eval needs --ema-decay")
+    if out:
+        out.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    return out
+
+
+def recipe_kwargs(config):
+    """the entries above as NativeTrainer's (lr_schedule, weight_decay, ema_decay) keywords; {} for a run without them"""
+    return {k: config[k] for k in ("lr_schedule", "weight_decay", "ema_decay") if k in config}
+
+
+def log_lr_stats(config, trainer, log_scalar, **tags):
+    """on a logging iteration of a run with a schedule / decay / average: lr of the last applied step and, with the average, ema_updates (a sync)"""
+    if not recipe_kwargs(config):
+        return None
+    st = trainer.lr_stats()
+    if st["lr"] is not None:                  # (None: no step has been applied yet)
+        log_scalar(lr=st["lr"], **tags)
+    if "ema_decay" in config:
+        log_scalar(ema_updates=st["ema_updates"], **tags)
+    return st
+
+
+def ema_eval(config, trainer):
+    """--ema-eval: the context the validation pass runs in (the averaged weights); without the flag a context that does nothing"""
+    return trainer.ema_weights() if config.get("ema_eval") else contextlib.nullcontext()
+
+
+def save_ema_model(config, trainer, epoch):
+    """--ema-decay: model-ema-%d.th beside model-%d.th, the same layout (the student's state_dict with the averaged parameters)"""
+    if "ema_decay" in config:
+        torch.save(trainer.ema_state_dict(), str(Path(config["log_dir"]) / ("model-ema-%d.th" % epoch)))
 
 
 def add_accumulate_argument(parser):
@@ -115,6 +206,7 @@ def config_entries(parsed):
         out.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
     out.update(clip_entries(parsed))
     out.update(accumulate_entries(parsed))
+    out.update(recipe_entries(parsed))
     return out
 
 

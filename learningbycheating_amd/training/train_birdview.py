@@ -41,6 +41,7 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
             if is_train:
                 resume.log_grad_stats(config, trainer, bzu.log.scalar, is_train=is_train)
+                resume.log_lr_stats(config, trainer, bzu.log.scalar, is_train=is_train)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
@@ -69,7 +70,7 @@ def train(config):
     data_train, data_val = make_loaders(config, device, rank, world)
     trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world,
                             skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
     loaders = {"train": data_train, "val": data_val}
     # --resume: the full state (train_state.th: optimizer, loaders, RNG, epoch) when there is one; without it, as before, the newest
     # model-%d.th with a fresh Adam from epoch 0
@@ -78,10 +79,12 @@ def train(config):
         net.train()
         train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
         net.eval()                              # reference train_birdview.py:175-176: validation pass after every epoch
-        train_or_eval(trainer, data_val, False, config, epoch == 0)
+        with resume.ema_eval(config, trainer):       # (--ema-eval: the validation pass sees the averaged weights)
+            train_or_eval(trainer, data_val, False, config, epoch == 0)
         net.train()
         if epoch in SAVE_EPOCHS and rank == 0:
             torch.save(net.state_dict(), str(Path(config["log_dir"]) / ("model-%d.th" % epoch)))
+            resume.save_ema_model(config, trainer, epoch)
         rec = bzu.log.end_epoch()
         if rank == 0:
             print(rec)

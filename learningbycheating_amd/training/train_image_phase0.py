@@ -47,6 +47,7 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
                 bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
             if is_train:
                 resume.log_grad_stats(config, trainer, bzu.log.scalar, is_train=is_train)
+                resume.log_lr_stats(config, trainer, bzu.log.scalar, is_train=is_train)
         now = time.time()
         bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
         tick = now
@@ -78,17 +79,19 @@ def train(config):
     cam = camera_struct(**{k: float(v) for k, v in config["camera_args"].items()})
     trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
                             skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
     loaders = {"train": data_train, "val": data_val}
     state = resume.load(config, trainer, loaders)
     for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):
         net.train()
         train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
         net.eval()                              # reference train_image_phase0.py:236-237: validation pass after every epoch
-        train_or_eval(trainer, data_val, False, config, epoch == 0)
+        with resume.ema_eval(config, trainer):       # (--ema-eval: the validation pass sees the averaged weights)
+            train_or_eval(trainer, data_val, False, config, epoch == 0)
         net.train()
         if epoch in SAVE_EPOCHS and rank == 0:
             torch.save(net.state_dict(), str(Path(config["log_dir"]) / ("model-%d.th" % epoch)))
+            resume.save_ema_model(config, trainer, epoch)
         rec = bzu.log.end_epoch()
         if rank == 0:
             print(rec)

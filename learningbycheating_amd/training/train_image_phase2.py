@@ -48,13 +48,24 @@ def phase2_weights(trainer, p_sel, t_sel):
 
 def _fresh_optimizer(trainer, config, lr):
     """fresh moments each epoch, as the reference re-creates its Adam there.  With --clip-grad-norm / --log-grad-norm the number of
-    clipped steps goes on counting across the epochs of a run (read and written at the epoch boundary, where the loop syncs anyway)."""
+    clipped steps goes on counting across the epochs of a run (read and written at the epoch boundary, where the loop syncs anyway).
+    --lr-schedule / --weight-decay go to every one of these optimizers: the schedule restarts with Adam's step count at every epoch."""
     clipped = trainer.opt.grad_stats()["clipped_total"]
     # (--accumulate: the optimizer reads the accumulation buffer; the loop closes every epoch at a window boundary)
     grads = trainer.accum_views if trainer.accum_views is not None else trainer.eng.grad_views
     trainer.opt = FusedAdam(list(trainer.student.named_parameters()), grads, lr=lr,
-                            guarded=config.get("skip_nonfinite", False), max_grad_norm=config.get("max_grad_norm"))
+                            guarded=config.get("skip_nonfinite", False), max_grad_norm=config.get("max_grad_norm"), **_recipe(config))
     trainer.opt.set_clipped(clipped)
+
+
+def _recipe(config):
+    """FusedAdam's keywords of --lr-schedule / --weight-decay; {} for a run without them"""
+    out = {}
+    if "lr_schedule" in config:
+        out["schedule"] = config["lr_schedule"]
+    if "weight_decay" in config:
+        out.update(weight_decay=config["weight_decay"], decoupled_weight_decay=True)
+    return out
 
 
 def _log_guard(trainer, config):
@@ -66,6 +77,7 @@ def _log_guard(trainer, config):
             raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
                                      % (row, config["max_skipped"]))
     resume.log_grad_stats(config, trainer, bzu.log.scalar)
+    resume.log_lr_stats(config, trainer, bzu.log.scalar)
 
 
 def _train(replay_buffer, trainer, config, episode):
@@ -267,6 +279,7 @@ def main(argv=None, on_epoch_end=None):
     parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
     resume.add_clip_arguments(parser)
     resume.add_accumulate_argument(parser)
+    resume.add_recipe_arguments(parser, per_epoch=True)
     parser.add_argument("--replay", choices=["host", "device"], default="host",
                         help="host = the replay buffer samples on the host and builds float batches; device = buffer, weighted sampling, uint8 gather "
                              "and weight write-back on the GPU, no host round trip inside a step")
@@ -279,6 +292,10 @@ def main(argv=None, on_epoch_end=None):
     parser.add_argument("--seed", type=int, default=None, help="with --replay device: seed torch's generators before the networks are built")
     parsed = parser.parse_args(argv)
     device_replay = parsed.replay == "device"
+    if parsed.ema_decay is not None or parsed.ema_eval:
+        raise SystemExit("train_image_phase2: --ema-decay is not available in phase 2: the optimizer is re-created every epoch and the state file "
+                         "is this script's own, so the average has nowhere to live yet (train phase 1 with it, or average afterwards)")
+    recipe = resume.recipe_entries(parsed)               # (a bad combination of flags exits here, before anything is built)
     if not device_replay:
         given = [f for f, on in (("--augment", parsed.augment != "None"), ("--batch_aug", parsed.batch_aug != 1), ("--save_state", parsed.save_state),
                                  ("--resume", parsed.resume), ("--seed", parsed.seed is not None)) if on]
@@ -303,6 +320,7 @@ def main(argv=None, on_epoch_end=None):
         config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
     config.update(resume.clip_entries(parsed))
     config.update(resume.accumulate_entries(parsed))
+    config.update(recipe)
     if device_replay:
         config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
                       world_size=world, synthetic_frames=True)
@@ -326,7 +344,7 @@ def main(argv=None, on_epoch_end=None):
     broadcast_module(teacher)
     trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
                             camera=camera_struct(), skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)))
+                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
     if device_replay:
         buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
