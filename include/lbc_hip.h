@@ -37,7 +37,9 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      new exports; lbc_adam_state and the guarded step are unchanged).  And once more: lbc_grad_accumulate (one new export, no
  *      record, nothing existing changed).  And again: lbc_adam_recipe, lbc_adam_recipe_state, lbc_adam_recipe_state_bytes,
  *      lbc_adam_step_recipe (a new descriptor, a new record type that starts with lbc_adam_clip_state's 64 bytes, new exports; the
- *      three existing steps and their records are unchanged).
+ *      three existing steps and their records are unchanged).  And the same way: lbc_waypoint_metrics_desc,
+ *      lbc_waypoint_metrics_state, lbc_waypoint_metrics_state_bytes, lbc_waypoint_metrics_update (a new descriptor, a new record
+ *      type, two new exports; nothing existing changed).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -363,6 +365,61 @@ int lbc_adam_step_recipe(const lbc_adam_chunk* chunks_dev, int nchunks, const lb
  * the kernel reads and writes through restrict-qualified pointers); n >= 0, n == 0 launches nothing.  One f32 add per
  * element in call order: no atomics, no reassociation -- the same inputs give the same bits on every run and every rank. */
 int lbc_grad_accumulate(const float* g, float* acc, long long n, int first, lbc_stream_t stream);
+
+/* Waypoint error metrics in metres, accumulated on the device (csrc/metrics.hip).  Not in the reference, which logs only the
+ * loss: displacement error of the COMMANDED branch's waypoints against the teacher (or the ground truth), per command and per
+ * horizon step, split into a lateral (map x) and a longitudinal (map y) part, with the share of waypoints inside given tolerances.
+ * One launch per batch adds that batch into the record below; nothing is read back until the host wants the numbers.
+ * Call sequence: hipMemset the record to zero once (all-zero bytes are the empty record), lbc_waypoint_metrics_update per batch
+ * on the stream of the loss, copy lbc_waypoint_metrics_state_bytes() bytes back where the host synchronises anyway.
+ * Per sample n: c = the index of the first non-zero entry of command_onehot[n] (none: the sample counts in `samples`, in the
+ * all-branch fields and in the loss, and in no commanded cell).  Per horizon step t < 5, in DOUBLE from the f32 inputs:
+ *   prediction, pred_frame 0 (camera frame, the image models): the unprojection of lbc_loss kind 1 --
+ *     xt = ((x + 1) w / 2 - w / 2) / f, yt = ((y + 1) h / 2 - h / 2) / f, f = w / (2 tan(fov pi / 360)) (computed on the host),
+ *     z = world_y / yt, px = z xt pixels_per_meter + crop_size / 2, py = crop_size - z pixels_per_meter + fixed_offset pixels_per_meter;
+ *   prediction, pred_frame 1 (map frame, the bird-view model): p = (v + 1) crop_size / 2;
+ *   target: q = (target * target_scale + target_shift + 1) crop_size / 2 (a normalised map coordinate after scale and shift);
+ *   dx = (px - qx) / pixels_per_meter, dy = (py - qy) / pixels_per_meter, e = sqrt(dx^2 + dy^2)   [metres].
+ * A row whose e is not finite (a prediction on the horizon row, yt = 0; a NaN or an infinity anywhere) counts in `bad` and in
+ * nothing else; cmd_count[c] - bad[c][t] is therefore the number of rows behind the sums of cell [c][t].
+ * rows = 20: pred / target are (N,4,5,2), the commanded rows are picked out of them and the all_* fields see every branch;
+ * rows = 5: pred / target are (N,5,2), the all_* fields are not touched.  loss (may be NULL: loss_* untouched): N per-sample values.
+ * One workgroup, no atomics, no workspace, every sum in a fixed order: a sequence of calls gives the same bits on every run.
+ * Reads stay inside pred / target / command_onehot / loss, writes inside the record.  N == 0 launches nothing.
+ * Refused with LBC_EINVAL (nothing launched, the record untouched): a null or non-8-byte-aligned state, null pred / target /
+ * command_onehot, N < 0, rows not 5 or 20, pred_frame not 0 or 1, nthresholds outside 0..4, a negative or non-finite threshold,
+ * a struct_size other than sizeof(lbc_waypoint_metrics_desc) (start it as `lbc_waypoint_metrics_desc d = LBC_WAYPOINT_METRICS_DESC_INIT;`). */
+typedef struct lbc_waypoint_metrics_desc {
+    unsigned struct_size;        /* = sizeof(lbc_waypoint_metrics_desc) */
+    int pred_frame;              /* 0: camera frame (unprojected), 1: map frame */
+    int rows;                    /* 5 or 20 */
+    int nthresholds;             /* 0..4 */
+    double target_scale, target_shift;
+    double thresholds_m[4];      /* metres; within[k] counts finite rows with e <= thresholds_m[k] */
+    lbc_camera camera;
+    int reserved;                /* zero */
+} lbc_waypoint_metrics_desc;
+#define LBC_WAYPOINT_METRICS_DESC_INIT { (unsigned)sizeof(lbc_waypoint_metrics_desc), 0, 5, 0, 1.0, 0.0, { 0.0, 0.0, 0.0, 0.0 }, \
+                                         { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, 0 }
+typedef struct lbc_waypoint_metrics_state {      /* 248 fields of 8 bytes; [c] command, [t] horizon step, [b] branch, [k] threshold */
+    long long samples;           /* samples seen */
+    long long updates;           /* launches (calls with N > 0) */
+    long long cmd_count[4];      /* samples per command */
+    double sum_e[4][5];          /* commanded branch, finite rows: sum of e */
+    double sum_e2[4][5];         /*   ... of e^2 */
+    double sum_abs_dx[4][5];     /*   ... of |dx| (lateral) */
+    double sum_abs_dy[4][5];     /*   ... of |dy| (longitudinal) */
+    double max_e[4][5];          /*   ... the largest e */
+    long long bad[4][5];         /* commanded rows whose e is not finite */
+    long long within[4][4][5];   /* [k][c][t]: finite rows with e <= thresholds_m[k]; k >= nthresholds untouched */
+    double all_sum_e[4][5];      /* rows = 20 only, every sample for branch b: sum of e over finite rows */
+    long long all_bad[4][5];     /*   ... rows whose e is not finite */
+    double loss_sum;             /* sum of the finite per-sample losses */
+    long long loss_bad;          /* per-sample losses that are not finite */
+} lbc_waypoint_metrics_state;
+size_t lbc_waypoint_metrics_state_bytes(void);
+int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const float* pred, const float* target, const float* command_onehot,
+                                const float* loss /* may be NULL */, int N, void* state, lbc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-operator entry points of the HBM-bound kernels: what the executor above launches between the

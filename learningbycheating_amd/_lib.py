@@ -88,6 +88,27 @@ class AdamRecipe(ctypes.Structure):
         super().__init__(**d)
 
 
+class WaypointMetricsDesc(ctypes.Structure):
+    """lbc_waypoint_metrics_desc (a host struct, read during the call); struct_size is filled in here"""
+    _fields_ = [("struct_size", ctypes.c_uint), ("pred_frame", c_int), ("rows", c_int), ("nthresholds", c_int),
+                ("target_scale", ctypes.c_double), ("target_shift", ctypes.c_double), ("thresholds_m", ctypes.c_double * 4),
+                ("camera", Camera), ("reserved", c_int)]
+
+    def __init__(self, **kw):
+        d = dict(struct_size=ctypes.sizeof(WaypointMetricsDesc), rows=5, target_scale=1.0)
+        d.update(kw)
+        super().__init__(**d)
+
+
+class WaypointMetricsState(ctypes.Structure):
+    """lbc_waypoint_metrics_state: the device record of the waypoint metrics, 248 fields of 8 bytes"""
+    _fields_ = [("samples", ctypes.c_longlong), ("updates", ctypes.c_longlong), ("cmd_count", ctypes.c_longlong * 4),
+                ("sum_e", ctypes.c_double * 5 * 4), ("sum_e2", ctypes.c_double * 5 * 4), ("sum_abs_dx", ctypes.c_double * 5 * 4),
+                ("sum_abs_dy", ctypes.c_double * 5 * 4), ("max_e", ctypes.c_double * 5 * 4), ("bad", ctypes.c_longlong * 5 * 4),
+                ("within", ctypes.c_longlong * 5 * 4 * 4), ("all_sum_e", ctypes.c_double * 5 * 4), ("all_bad", ctypes.c_longlong * 5 * 4),
+                ("loss_sum", ctypes.c_double), ("loss_bad", ctypes.c_longlong)]
+
+
 _SIGNATURES = {
     "lbc_last_error": (c_char_p, []),
     "lbc_backend": (c_char_p, []),
@@ -134,6 +155,8 @@ _SIGNATURES = {
     "lbc_adam_recipe_state_bytes": (c_size_t, [c_int]),
     "lbc_adam_step_recipe": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lbc_grad_accumulate": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
+    "lbc_waypoint_metrics_state_bytes": (c_size_t, []),
+    "lbc_waypoint_metrics_update": (c_int, [ctypes.POINTER(WaypointMetricsDesc)] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
     "lbc_bn_stats": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "lbc_bn_finalize_stats": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 5),
     "lbc_bn_apply_relu_add_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),

@@ -56,6 +56,17 @@ int lbc_grad_accumulate(const float* g, float* acc, long long n, int first, lbc_
     return lbc_grad_accumulate_launch(g, acc, n, first, (hipStream_t)stream);
 }
 
+size_t lbc_waypoint_metrics_state_bytes(void) { return sizeof(lbc_waypoint_metrics_state); }
+
+int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const float* pred, const float* target, const float* command_onehot,
+                                const float* loss, int N, void* state, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_waypoint_metrics_desc) == 96 && offsetof(lbc_waypoint_metrics_desc, target_scale) == 16 &&
+                  offsetof(lbc_waypoint_metrics_desc, thresholds_m) == 32 && offsetof(lbc_waypoint_metrics_desc, camera) == 64,
+                  "lbc_waypoint_metrics_desc layout (include/lbc_hip.h)");
+    return lbc_waypoint_metrics_launch(desc, pred, target, command_onehot, loss, N, state, (hipStream_t)stream);
+}
+
 // Every entry point that takes a descriptor checks it: struct_size must cover the fields of the first checked layout (ABI 200: everything up to
 // and including split_workspace_bytes) and must not exceed this library's struct.  A host built against an OLDER header of the same major
 // ABI (fewer trailing fields) stays valid: whoever appends a field must read it only where struct_size covers it (today the checked

@@ -285,3 +285,8 @@ int lbc_adam_recipe_launch(const AdamChunk* chunks_dev, int nchunks, const lbc_a
                            lbc_adam_recipe_state* state_dev, hipStream_t s);
 // grad_accum.hip: acc = first ? g : acc + g over n floats (gradient accumulation over micro-batches); one launch, no atomics
 int lbc_grad_accumulate_launch(const float* g, float* acc, long long n, int first, hipStream_t s);
+// metrics.hip: one launch adds a batch's waypoint errors in metres (commanded branch, per command and horizon step) into the device
+// record lbc_waypoint_metrics_state (include/lbc_hip.h); one workgroup, no atomics, fixed summation order.  The descriptor is validated here.
+struct lbc_waypoint_metrics_desc;
+int lbc_waypoint_metrics_launch(const lbc_waypoint_metrics_desc* d, const float* pred, const float* target, const float* command_onehot,
+                                const float* loss, int N, void* state, hipStream_t s);

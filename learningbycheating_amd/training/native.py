@@ -65,6 +65,13 @@ class NativeTrainer:
     `with trainer.ema_weights():` runs on them.  Under data parallelism the ranks agree bit for bit: lr is a function of the record's
     step, the average a function of identical updated parameters.
 
+    step(..., metrics=m) (training/metrics.py WaypointMetrics; default None: the launches of a step are exactly what they were): right
+    behind the loss launch, on its stream, the step adds this batch's waypoint errors in metres into m's device record -- from the
+    tensors the loss just read and the per-sample loss it wrote (phase 1 / 'l1_all': all four branches, the commanded rows picked out
+    on the device; phase 0 / bird-view: the selected branch).  One small launch that only reads: it works for updating and
+    non-updating steps, in train and eval mode, and never syncs.  `make_metrics()` builds an object that fits this trainer's phase;
+    one whose frame (or, for bird-view, target scale / shift) does not fit is refused with ValueError before anything is launched.
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
@@ -140,7 +147,27 @@ class NativeTrainer:
         _lib.check(_lib.get().lbc_loss(kind, ctypes.byref(self.cam), _lib.ptr(pred), _lib.ptr(target), n, rows,
                                        1.0 / (n * self.world * self.accumulate), _lib.ptr(self.loss), _lib.ptr(dpred), _lib.stream_for(pred)), "loss")
 
-    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None):
+    def _metrics_frame(self):
+        """(pred_frame, target_scale, target_shift) of a WaypointMetrics that fits this trainer's loss"""
+        if self.phase == "birdview":
+            return "map", 1.0 / (0.5 * float(self.cam.crop_size)), -1.0       # lbc_loss kind 2: ground truth in crop pixels
+        return "camera", 1.0, 0.0
+
+    def make_metrics(self, thresholds=(0.5, 1.0, 2.0)):
+        from .metrics import WaypointMetrics
+        frame, scale, shift = self._metrics_frame()
+        return WaypointMetrics(self.device, camera=self.cam, pred_frame=frame, thresholds=thresholds, target_scale=scale, target_shift=shift)
+
+    def _check_metrics(self, metrics):
+        frame, scale, shift = self._metrics_frame()
+        if metrics.pred_frame != frame:
+            raise ValueError("NativeTrainer.step: phase %r predicts in the %s frame, the metrics object was built for the %s frame"
+                             % (self.phase, frame, metrics.pred_frame))
+        if (metrics.target_scale, metrics.target_shift) != (scale, shift):
+            raise ValueError("NativeTrainer.step: phase %r compares against target * %r + %r, the metrics object was built for target * %r + %r"
+                             % (self.phase, scale, shift, metrics.target_scale, metrics.target_shift))
+
+    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None, metrics=None):
         """x: student input, float32 (N,C,H,W) in [0,1] or the dataset's uint8 (N,H,W,C) frames; command one-hot (N,4);
         returns the per-sample loss (device tensor).  update=False: forward + loss only.  train_mode=False: the student runs
         in eval mode (running statistics, no buffer update) -- the reference's validation pass (train_image_phase1.py:162-165,256).
@@ -149,6 +176,8 @@ class NativeTrainer:
             raise ValueError("an eval-mode step cannot update (backward through running-statistics BatchNorm is not implemented)")
         if update and self._in_ema_weights:
             raise RuntimeError("NativeTrainer.step: an updating step inside ema_weights() would train the average")
+        if metrics is not None:
+            self._check_metrics(metrics)
         n = x.shape[0]
         # the executor takes raw pointers to dense tensors; a permuted / sliced view is packed first (the reference's
         # nn.Module accepts any strides)
@@ -188,6 +217,12 @@ class NativeTrainer:
             self._loss(3, p_all, target, 20, self.dpred_all); d_all = self.dpred_all[:n]
         else:
             raise ValueError(self.phase)
+        if metrics is not None:
+            # the tensors the loss just read, the per-sample loss it just wrote, on its stream; the kernel only reads them
+            if self.phase in (1, "l1_all"):
+                metrics.update(p_all, t_all if self.phase == 1 else target, command, self.loss[:n])
+            else:
+                metrics.update(p_sel, t_sel if self.phase == 0 else target, command, self.loss[:n])
         if update and self.accumulate > 1:
             self._accumulating_backward(d_sel, d_all)
         elif update:

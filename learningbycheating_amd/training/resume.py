@@ -1,5 +1,5 @@
 """What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate /
---lr-schedule / --weight-decay / --ema-decay.
+--lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -31,6 +31,65 @@ def add_arguments(parser, with_resume=True):
     add_clip_arguments(parser)
     add_accumulate_argument(parser)
     add_recipe_arguments(parser)
+    add_metrics_arguments(parser)
+
+
+def add_metrics_arguments(parser):
+    parser.add_argument("--val-metrics", action="store_true",
+                        help="the validation pass accumulates waypoint errors in metres on the device (commanded branch: ADE / FDE, per "
+                             "command, lateral / longitudinal, share inside 0.5 / 1 / 2 m) and reads them back once, after its last batch, "
+                             "instead of reading the loss back after every batch.  Default: off")
+    parser.add_argument("--train-metrics", action="store_true",
+                        help="the training pass accumulates the same errors and logs ade / fde / bad_rows since the previous logging "
+                             "iteration on every logging iteration.  Default: off")
+
+
+def metrics_entries(parsed):
+    """config entries of --val-metrics / --train-metrics; a run without them writes the config.json it always wrote"""
+    out = {}
+    if getattr(parsed, "val_metrics", False):
+        out["val_metrics"] = True
+    if getattr(parsed, "train_metrics", False):
+        out["train_metrics"] = True
+    return out
+
+
+def pass_metrics(config, trainer, is_train):
+    """the WaypointMetrics object a pass hands to every trainer.step, emptied: the validation pass's with --val-metrics, the training
+    pass's with --train-metrics, None otherwise (the step then launches what it always launched).  One object per trainer and kind,
+    made on first use."""
+    if not config.get("train_metrics" if is_train else "val_metrics"):
+        return None
+    kept = trainer.__dict__.setdefault("_pass_metrics", {})
+    if is_train not in kept:
+        kept[is_train] = trainer.make_metrics()
+    kept[is_train].reset()
+    return kept[is_train]
+
+
+def log_val_metrics(config, metrics, log_scalar, nonfinite=None):
+    """the end of a validation pass with --val-metrics: one all_gather of the record under WORLD_SIZE > 1, one read-back (the pass's
+    only sync), then loss_mean -- the pass's mean over its samples -- and ade, fde, ade_cmd1..4, fde_cmd1..4 (absent commands left out),
+    lateral, longitudinal, within_<thr> and bad_rows, which the epoch record holds as val_ade, val_fde, ... beside val_loss_mean.  nonfinite: the message of the
+    FloatingPointError raised when a per-sample loss was not finite and --skip-nonfinite is off (phase 1).  -> the result"""
+    from .metrics import log_entries
+    res = metrics.result(metrics.all_gather() if config["world_size"] > 1 else None)
+    if nonfinite is not None and res["loss_bad"] > 0 and not config.get("skip_nonfinite"):
+        raise FloatingPointError(nonfinite % ("non-finite for %d of %d samples" % (res["loss_bad"], res["samples"])))
+    if res["loss_mean"] is not None:
+        log_scalar(is_train=False, loss_mean=res["loss_mean"])
+    log_scalar(is_train=False, **log_entries(res))
+    return res
+
+
+def log_train_metrics(metrics, log_scalar):
+    """a logging iteration of a training pass with --train-metrics (the loop syncs there anyway): ade / fde / bad_rows of this rank's
+    batches since the previous logging iteration, then the record is emptied"""
+    res = metrics.result()
+    entries = {k: res[k] for k in ("ade", "fde") if res[k] is not None}
+    log_scalar(is_train=True, bad_rows=res["bad_rows"], **entries)
+    metrics.reset()
+    return res
 
 
 def add_recipe_arguments(parser, per_epoch=False):
@@ -207,6 +266,7 @@ def config_entries(parsed):
     out.update(clip_entries(parsed))
     out.update(accumulate_entries(parsed))
     out.update(recipe_entries(parsed))
+    out.update(metrics_entries(parsed))
     return out
 
 

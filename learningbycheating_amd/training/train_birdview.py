@@ -28,12 +28,16 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
     tick = time.time()
     update = is_train and not is_first_epoch
     windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
+    metrics = resume.pass_metrics(config, trainer, is_train)         # (--val-metrics / --train-metrics; None without them)
+    sync_free = metrics is not None and not is_train                 # the validation pass with --val-metrics reads nothing back per batch
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
-        loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=update, train_mode=is_train)
+        loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=update, train_mode=is_train, metrics=metrics)
         windows.after_step(update)
-        if (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch:
+        if ((i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch) and not sync_free:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
+            if metrics is not None:
+                resume.log_train_metrics(metrics, bzu.log.scalar)
             if update:
                 windows.log(bzu.log.scalar, is_train=is_train)
             skipped = resume.check_skipped(config, trainer, "train_birdview") if is_train else None
@@ -51,6 +55,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             break
     if update:
         windows.end_pass(bzu.log.scalar, is_train=is_train)
+    if sync_free:
+        resume.log_val_metrics(config, metrics, bzu.log.scalar)
 
 
 def train(config):

@@ -63,15 +63,17 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
     device = config["device"]
     update = is_train and not is_first_epoch
     windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
+    metrics = resume.pass_metrics(config, trainer, is_train)         # (--val-metrics / --train-metrics; None without them)
+    sync_free = metrics is not None and not is_train                 # the validation pass with --val-metrics reads nothing back per batch
     # (a loader restored in the middle of its pass hands out the rest of it: the iteration count goes on where it stood)
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(device)
         if is_train and config["speed_noise"] > 0:
             speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
-        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train)
+        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train, metrics=metrics)
         windows.after_step(update)
         should_log = (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch
-        if should_log:
+        if should_log and not sync_free:
             lm = loss.mean().item()          # device->host sync only when logging, as the reference (:207-221)
             skipped = resume.check_skipped(config, trainer, "phase 1") if is_train else None
             if skipped is not None:
@@ -83,6 +85,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
                 raise FloatingPointError("phase-1 loss is %s: a predicted waypoint reached the horizon (1/y pole of the "
                                          "unprojection); start from a phase-0 checkpoint" % lm)
             bzu.log.scalar(is_train=is_train, loss_mean=lm)
+            if metrics is not None:
+                resume.log_train_metrics(metrics, bzu.log.scalar)
             if update:
                 windows.log(bzu.log.scalar, is_train=is_train)
         now = time.time()
@@ -94,6 +98,10 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
             break
     if update:
         windows.end_pass(bzu.log.scalar, is_train=is_train)
+    if sync_free:
+        resume.log_val_metrics(config, metrics, bzu.log.scalar,
+                               nonfinite="phase-1 validation loss is %s: a predicted waypoint reached the horizon (1/y pole of the "
+                                         "unprojection); start from a phase-0 checkpoint")
 
 
 def train(config):
