@@ -261,24 +261,22 @@ int lbc_loss_phase0(const LossArgs& a, hipStream_t s);   // teacher map -> image
 int lbc_loss_l1(const LossArgs& a, float target_scale, float target_shift, hipStream_t s);   // bird-view BC loss
 int lbc_phase2_weight_launch(const LossArgs& a, hipStream_t s);   // DAgger resampling weights (selected branch, map space)
 
-// ---- Adam (multi-tensor) ------------------------------------------------------------------
+// ---- Adam (multi-tensor), adam.hip ---------------------------------------------------------
 struct AdamChunk { float* p; const float* g; float* m; float* v; int n; int pad; };
 int lbc_adam_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int step, hipStream_t s);
-long long lbc_adam_profile_elems_get();      // what lbc_adam_profile_elems() was last given
-// adam_guarded.hip: non-finite scan of the gradients -> bookkeeping on the device record -> the same update, skipped as a whole when
-// the scan found something.  No device-to-host traffic; the step count lives in *state_dev (include/lbc_hip.h lbc_adam_state).
+// guarded: non-finite scan of the gradients -> bookkeeping on the device record -> the same update, skipped as a whole when the scan
+// found something.  No device-to-host traffic; the step count lives in *state_dev (include/lbc_hip.h lbc_adam_state).
 struct lbc_adam_state;
 int lbc_adam_guarded_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, lbc_adam_state* state_dev, hipStream_t s);
-// adam_clip.hip: the guarded step whose gradient pass also sums the squares -> global norm, clipping coefficient and skip decision on
-// the device record (include/lbc_hip.h lbc_adam_clip_state + one double per chunk) -> the guarded update on g * clip_coef.
+// clipped: the guarded step whose gradient pass also sums the squares -> global norm, clipping coefficient and skip decision on the
+// device record (include/lbc_hip.h lbc_adam_clip_state + one double per chunk) -> the guarded update on g * clip_coef.
 struct lbc_adam_clip_state;
 int lbc_adam_clipped_launch(const AdamChunk* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,
                             double weight_decay, double max_norm, lbc_adam_clip_state* state_dev, hipStream_t s);
-void lbc_adam_norm_pass(const AdamChunk* chunks_dev, int nchunks, lbc_adam_clip_state* state_dev, double* partial, hipStream_t s);   // its first launch alone
-// adam_recipe.hip: the clipped step with a learning-rate schedule evaluated in the bookkeeping thread, decoupled weight decay and an
-// exponential moving average of the parameters (include/lbc_hip.h lbc_adam_recipe / lbc_adam_recipe_state).  The recipe is validated here.
+// recipe: the clipped step with a learning-rate schedule evaluated in the bookkeeping thread, decoupled weight decay and an exponential
+// moving average of the parameters (include/lbc_hip.h lbc_adam_recipe / lbc_adam_recipe_state).  The recipe is validated there.
 struct lbc_adam_recipe;
 struct lbc_adam_recipe_state;
 int lbc_adam_recipe_launch(const AdamChunk* chunks_dev, int nchunks, const lbc_adam_recipe* recipe, float* const* ema_dev,

@@ -13,7 +13,7 @@ CHUNK = 32768
 
 @dataclasses.dataclass(frozen=True)
 class LRSchedule:
-    """The learning-rate schedule of FusedAdam's recipe path (csrc/adam_recipe.hip), evaluated on the device at k = the number of updates
+    """The learning-rate schedule of FusedAdam's recipe path (csrc/adam.hip), evaluated on the device at k = the number of updates
     applied so far: k < warmup_steps: base * (warmup_start + (1 - warmup_start) * k / warmup_steps); afterwards, with j = k - warmup_steps,
     "constant": base; "cosine": min_lr + (base - min_lr) * 0.5 * (1 + cos(pi * min(j, T - W) / (T - W))) with T = total_steps;
     "step": base * gamma ** (j // step_size).  The base rate is the optimizer's `lr`."""
@@ -53,12 +53,12 @@ class FusedAdam:
     """Adam over (param, grad) pairs whose physical memory is dense (any stride permutation);
     grads are the engine's flat-buffer views, so p, g, m, v share one element order.
 
-    guarded=True: every step first scans the gradients for NaN / +-Inf on the device (csrc/adam_guarded.hip) and skips the whole
+    guarded=True: every step first scans the gradients for NaN / +-Inf on the device (csrc/adam.hip) and skips the whole
     update when it finds one -- parameters, both moments and the step count keep their bits.  The step count then lives in a device
     record (lbc_adam_state), no step ever syncs; `step_count` and `skipped()` read the record back (a device-to-host copy: for logging
     and checkpoints only).
 
-    max_grad_norm=X (a number; implies guarded): the gradient pass of the guard also sums the squares (csrc/adam_clip.hip), and the update
+    max_grad_norm=X (a number; implies guarded): the gradient pass of the guard also sums the squares (csrc/adam.hip), and the update
     multiplies every gradient element by torch.nn.utils.clip_grad_norm_'s coefficient min(1, X / (norm + 1e-6)), all on the device and
     still without a sync.  X = 0 measures the norm and never clips.  THE GRADIENT VIEWS KEEP THE UNCLIPPED VALUES: the coefficient is
     applied inside the update, the gradient buffer is not written.  `grad_stats()` reads norm, coefficient and the number of clipped
@@ -66,7 +66,7 @@ class FusedAdam:
     `max_grad_norm` of a clipped optimizer may be assigned another number between steps: step() passes its current value with every
     call (the choice between the clipped and the other paths is made once, here).
 
-    schedule=... / decoupled_weight_decay=True / ema_decay=D: any of them selects the recipe path (csrc/adam_recipe.hip), built like the
+    schedule=... / decoupled_weight_decay=True / ema_decay=D: any of them selects the recipe path (csrc/adam.hip), built like the
     clipped step and like it without a sync; it always guards and always measures the norm (max_grad_norm=None measures only there).
     `schedule` (an LRSchedule or a dict of its fields) makes `lr` the BASE rate: the rate of a step is a function of the device record's
     step count, which a skipped step does not advance.  decoupled_weight_decay: p *= 1 - lr * weight_decay in front of the update
@@ -101,7 +101,7 @@ class FusedAdam:
         self.all_names = [n for n, _ in named_params]
         self.names = [n for n, _ in named_params if n in grads]
         params = dict(named_params)
-        # moments in the gradients' element order, every tensor starting on a 64-element (256-byte) boundary: adam_k moves
+        # moments in the gradients' element order, every tensor starting on a 64-element (256-byte) boundary: adam_update_k moves
         # 16 bytes per lane, so p, g, m and v of every chunk must be 16-byte aligned (the engine's flat gradient buffer pads
         # the same way; the 5-element head biases would otherwise misalign everything behind them)
         from .engine import _pad
@@ -126,39 +126,35 @@ class FusedAdam:
             table[i] = r + (0,)
         assert table.itemsize == ctypes.sizeof(_lib.AdamChunk)
         self.nchunks = len(rows)
-        _lib.get().lbc_adam_profile_elems(sum(params[n].numel() for n in self.names))     # (books the launch profiler's 28 bytes per element)
+        lib = _lib.get()
+        lib.lbc_adam_profile_elems(sum(params[n].numel() for n in self.names))     # (books the launch profiler's 28 bytes per element)
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev)
         self._keep = (params, grads)
+        # one device record per guarded mode: its header and, from the clipped step on, one partial sum of squares per chunk behind it
+        self._State, nbytes = ((None, 0) if not self.guarded else
+                               (_lib.AdamRecipeState, lib.lbc_adam_recipe_state_bytes(self.nchunks)) if self.recipe else
+                               (_lib.AdamClipState, lib.lbc_adam_clip_state_bytes(self.nchunks)) if self.clipped else
+                               (_lib.AdamState, lib.lbc_adam_state_bytes()))
         self.record = None
-        self._State = _lib.AdamRecipeState if self.recipe else _lib.AdamClipState if self.clipped else _lib.AdamState
+        if self.guarded:
+            assert int(nbytes) == ctypes.sizeof(self._State) + (8 * self.nchunks if self.clipped else 0), "lbc_%s layout" % self._State.__name__
+            self.record = torch.zeros(int(nbytes), dtype=torch.uint8, device=dev)      # (torch allocations are 256-byte aligned)
         self.ema, self.ema_table = None, None
-        if self.recipe:
-            nbytes = int(_lib.get().lbc_adam_recipe_state_bytes(self.nchunks))     # the header + one partial sum of squares per chunk
-            assert nbytes == ctypes.sizeof(_lib.AdamRecipeState) + 8 * self.nchunks, "lbc_adam_recipe_state layout"
-            self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-            if self.ema_decay is not None:
-                if ema is None:
-                    ema = torch.zeros(total, dtype=torch.float32, device=dev)
-                    fresh = True
-                else:
-                    if ema.dtype != torch.float32 or ema.numel() != total or not ema.is_contiguous() or ema.device != self.exp_avg.device:
-                        raise ValueError("FusedAdam: the ema buffer must be a contiguous float32 tensor of %d elements on %s" % (total, dev))
-                    fresh = False
-                assert ema.data_ptr() % 16 == 0, "adam: the ema buffer is not 16-byte aligned"
-                self.ema = ema
-                if fresh:
-                    for n in self.names:
-                        self.ema_of(n).copy_(params[n].data)
-                ptrs = np.array([self.ema.data_ptr() + (r[2] - self.exp_avg.data_ptr()) for r in rows], dtype=np.uint64)
-                self.ema_table = torch.from_numpy(ptrs.view(np.int64).copy()).to(dev)   # one float* per chunk: the chunk's slice of the shadow
-        elif self.clipped:
-            nbytes = int(_lib.get().lbc_adam_clip_state_bytes(self.nchunks))       # the header + one partial sum of squares per chunk
-            assert nbytes == ctypes.sizeof(_lib.AdamClipState) + 8 * self.nchunks, "lbc_adam_clip_state layout"
-            self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        elif self.guarded:
-            nbytes = int(_lib.get().lbc_adam_state_bytes())
-            assert nbytes == ctypes.sizeof(_lib.AdamState), "lbc_adam_state layout"
-            self.record = torch.zeros(nbytes, dtype=torch.uint8, device=dev)       # (torch allocations are 256-byte aligned)
+        if self.ema_decay is not None:
+            if ema is None:
+                ema = torch.zeros(total, dtype=torch.float32, device=dev)
+                fresh = True
+            else:
+                if ema.dtype != torch.float32 or ema.numel() != total or not ema.is_contiguous() or ema.device != self.exp_avg.device:
+                    raise ValueError("FusedAdam: the ema buffer must be a contiguous float32 tensor of %d elements on %s" % (total, dev))
+                fresh = False
+            assert ema.data_ptr() % 16 == 0, "adam: the ema buffer is not 16-byte aligned"
+            self.ema = ema
+            if fresh:
+                for n in self.names:
+                    self.ema_of(n).copy_(params[n].data)
+            ptrs = np.array([self.ema.data_ptr() + (r[2] - self.exp_avg.data_ptr()) for r in rows], dtype=np.uint64)
+            self.ema_table = torch.from_numpy(ptrs.view(np.int64).copy()).to(dev)   # one float* per chunk: the chunk's slice of the shadow
 
     # ---- the step ---------------------------------------------------------------------------
     def _recipe_struct(self):
@@ -193,24 +189,20 @@ class FusedAdam:
         head = self.record[:ctypes.sizeof(self._State)]
         return self._State.from_buffer_copy(head.cpu().numpy().tobytes())       # (the copy waits for the steps in flight)
 
-    def _write_record(self, step, skipped_total=0, skipped_in_a_row=0, clipped_total=None, ema_updates=None):
-        # the coefficients stay zero: the bookkeeping kernel derives them from `step` before the next applied update reads them
-        if self.recipe:
-            # as below; the last clean step's rate and decay factor are telemetry too, the number of average updates is a counter
+    def _write_record(self, **counters):
+        """read-modify-write of the header: sets the counters that are passed (step, skipped_total, skipped_in_a_row, clipped_total,
+        ema_updates -- the latter two only where the record has them) and keeps the rest, telemetry of the last clean step included"""
+        rec = self._read_record()
+        if self.recipe and rec.step == 0:
             # A record that has not applied a step holds no rate: NaN marks "not computed since the step count was set from outside" (a
             # resume), which lr_stats() reports as None until the next clean step writes the schedule's value at that count
-            old = self._read_record()
-            lr, df = (old.lr, old.decay_factor) if old.step > 0 else (float("nan"), float("nan"))
-            rec = _lib.AdamRecipeState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0, old.grad_norm, old.clip_coef, 0,
-                                       int(old.clipped_total if clipped_total is None else clipped_total), lr, df, 0,
-                                       int(old.ema_updates if ema_updates is None else ema_updates))
-        elif self.clipped:
-            # norm and coefficient of the last clean step are telemetry: they are kept, as is the count unless a new one is given
-            old = self._read_record()
-            rec = _lib.AdamClipState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0, old.grad_norm, old.clip_coef, 0,
-                                     int(old.clipped_total if clipped_total is None else clipped_total))
-        else:
-            rec = _lib.AdamState(int(step), int(skipped_total), int(skipped_in_a_row), 0, 0, 0.0, 0.0)
+            rec.lr = rec.decay_factor = float("nan")
+        for name, value in counters.items():
+            assert hasattr(type(rec), name), "%s has no %s" % (type(rec).__name__, name)
+            setattr(rec, name, int(value))
+        # the coefficients are zeroed: the bookkeeping kernel derives them from `step` before the next applied update reads them
+        rec.bad = rec.scan_flag = 0
+        rec.lr_over_bc1 = rec.inv_bc2_sqrt = 0.0
         self.record[:ctypes.sizeof(rec)].copy_(torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8))
 
     @property
@@ -221,8 +213,7 @@ class FusedAdam:
     @step_count.setter
     def step_count(self, value):
         if self.guarded:
-            r = self._read_record()
-            self._write_record(value, r.skipped_total, r.skipped_in_a_row)
+            self._write_record(step=value)
         else:
             self._step_count = int(value)
 
@@ -235,7 +226,7 @@ class FusedAdam:
 
     def set_skipped(self, total, in_a_row):
         if self.guarded:
-            self._write_record(self._read_record().step, total, in_a_row)
+            self._write_record(skipped_total=total, skipped_in_a_row=in_a_row)
 
     def grad_stats(self):
         """{"grad_norm", "clip_coef", "clipped_total"} of the clipped mode: global L2 norm of the gradients (before clipping) and the
@@ -248,8 +239,7 @@ class FusedAdam:
 
     def set_clipped(self, total):
         if self.clipped:
-            r = self._read_record()
-            self._write_record(r.step, r.skipped_total, r.skipped_in_a_row, clipped_total=total)
+            self._write_record(clipped_total=total)
 
     def lr_stats(self):
         """{"lr", "ema_updates"}: the rate the schedule gave the last applied step and the number of applied steps that moved the average.
@@ -263,8 +253,7 @@ class FusedAdam:
 
     def set_ema_updates(self, total):
         if self.recipe:
-            r = self._read_record()
-            self._write_record(r.step, r.skipped_total, r.skipped_in_a_row, ema_updates=total)
+            self._write_record(ema_updates=total)
 
     def ema_of(self, name):
         """the moving average of `name` as a view of `ema` in the parameter's logical shape"""

@@ -56,7 +56,7 @@ class NativeTrainer:
     abandons an open window; `step(update=False)` never touches the window.
 
     lr_schedule=... / weight_decay=X / ema_decay=D (any of them implies the guard and the norm measurement: FusedAdam's recipe path,
-    csrc/adam_recipe.hip).  lr_schedule (an optim.LRSchedule or a dict of its fields) makes `lr` the base rate of a schedule that the
+    csrc/adam.hip).  lr_schedule (an optim.LRSchedule or a dict of its fields) makes `lr` the base rate of a schedule that the
     optimizer's bookkeeping thread evaluates at Adam's own step count: a skipped step does not advance it, with accumulate=K it advances
     once per window, and no step syncs.  weight_decay is DECOUPLED (torch.optim.AdamW; every parameter, BatchNorm and biases included,
     as AdamW with one group).  ema_decay keeps an exponential moving average of the student's parameters (`opt.ema`), updated inside

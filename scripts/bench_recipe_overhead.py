@@ -1,4 +1,4 @@
-"""Cost of the optimizer's recipe path (NativeTrainer(lr_schedule=..., weight_decay=..., ema_decay=...): csrc/adam_recipe.hip) over the
+"""Cost of the optimizer's recipe path (NativeTrainer(lr_schedule=..., weight_decay=..., ema_decay=...): csrc/adam.hip) over the
 clipped step it is built like, on bench.py's phase-1 step, measured in one process.
 
     python scripts/bench_recipe_overhead.py [--batches 256,32] [--dtype bf16] [--steps 60] [--block 10] [--warmup 10] [--out FILE]

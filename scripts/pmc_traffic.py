@@ -18,7 +18,7 @@ def load(path, counter):
 
 
 def short(name):
-    m = re.search(r"(conv\w*_k|conv3x3_c64_k|splitk_reduce\w*|stem_\w+_k|bn_\w+_k|channel_reduce_k|adam_k|maxpool\w+_k|head_\w+_k|weight_prep_k)", name)
+    m = re.search(r"(conv\w*_k|conv3x3_c64_k|splitk_reduce\w*|stem_\w+_k|bn_\w+_k|channel_reduce_k|adam_\w+_k|maxpool\w+_k|head_\w+_k|weight_prep_k)", name)
     return m.group(1) if m else name[:48]
 
 

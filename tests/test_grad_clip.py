@@ -1,4 +1,4 @@
-"""Gradient clipping by global norm on the device, and the grad-norm telemetry (csrc/adam_clip.hip, lbc_adam_step_clipped).
+"""Gradient clipping by global norm on the device, and the grad-norm telemetry (csrc/adam.hip, lbc_adam_step_clipped).
 
 1. the norm: grad_norm^2 against a float64 sum over the logical elements, the padding between tensors poisoned with NaN;
 2. the same gradients give the same 8 bytes of grad_norm;

@@ -1,4 +1,4 @@
-"""The recipe path of the fused optimizer (csrc/adam_recipe.hip, lbc_adam_step_recipe): learning-rate schedule on the device, decoupled
+"""The recipe path of the fused optimizer (csrc/adam.hip, lbc_adam_step_recipe): learning-rate schedule on the device, decoupled
 weight decay and the moving average of the weights inside the update.
 
 1. a neutral recipe (constant, no warm-up, coupled decay, no average) is lbc_adam_step_clipped bit for bit, record included;
