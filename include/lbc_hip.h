@@ -556,6 +556,30 @@ int lbc_replay_scatter_u8(const unsigned char* src, long long row_bytes, const i
 int lbc_replay_meta(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, lbc_stream_t stream);
 int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, lbc_stream_t stream);
 
+/* Device-resident LMDB dataset (bird_view/utils/datasets/resident.py): the per-sample work of the host loader -- frame look-up, crop or
+ * rotation of the bird-view map, waypoints -- over a batch of frames that live in HBM.  The host draws and uploads one record of four
+ * int32 per sample, `draws[b] = (frame index, delta_angle in degrees, dx, dy)`; every call only enqueues on `stream`.  Indices are
+ * trusted (no frame count is passed): the caller checks them on the host before it uploads them.  Offsets are 64-bit throughout.
+ * (Exports added without a new ABI number; existing signatures unchanged.)
+ * lbc_dataset_gather_crop_u8: dst[b * reps + r] = the window rows [y0, y0 + H), columns [x0, x0 + W) of src frame idx[b]; src
+ *   [F][SH][SW][C], dst [B * reps][H][W][C].  Moves 16 bytes per lane when W * C, x0 * C, SW * C, SH * SW * C and both base pointers are
+ *   multiples of 16, a byte per lane otherwise.  With the whole frame as the window this is an indexed row gather.
+ * lbc_dataset_gather_warp_crop_u8: lbc_birdview_warp_crop_u8 through the record -- source frame draws[b].idx, inverted matrix
+ *   table[draws[b].delta_angle + A].im (2 A + 1 entries, one per integer angle in [-A, A]; their y0 / x0 are not read), window origin
+ *   rows draws[b].dy + (260 - H / 2) - H / 2, columns draws[b].dx + 160 - W / 2 (the ego pixel (160, 260) of the stored 320 x 320 map).
+ *   The same per-pixel arithmetic as lbc_birdview_warp_crop_u8: equal inputs give equal bytes.
+ * lbc_dataset_targets: loc[(b * reps + r)][k] (n_step x 2 f32, pixels of the crop) and speed[b * reps + r] of sample draws[b].idx from
+ *   the measurement table [rows][5] f32 = (x, y, heading, speed, cmd), one row per stored frame, episodes contiguous; the sample's row
+ *   is row_of_sample[idx], its k-th future position row + (k + 1) * gap (the caller guarantees that these rows belong to the same
+ *   episode).  Restates the reference's image_lmdb.py:143-163 / birdview_lmdb.py:127-141: (x - ox) * 5 in f32, angle = heading +
+ *   delta_angle * pi / 180 and everything after it in double, one cast to f32 at the end. */
+int lbc_dataset_gather_crop_u8(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
+                               unsigned char* dst, lbc_stream_t stream);
+int lbc_dataset_gather_warp_crop_u8(const unsigned char* src, const int* draws, const lbc_warp_params* table, int A, int B, int reps, int SH, int SW,
+                                    int C, int H, int W, unsigned char* dst, lbc_stream_t stream);
+int lbc_dataset_targets(const float* table, const int* row_of_sample, const int* draws, int B, int reps, int gap, int n_step, int img_size, int crop_size,
+                        float* loc, float* speed, lbc_stream_t stream);
+
 /* Runtime options (A/B switches, tuning knobs, test hooks): names are the LBC_* environment variables that initialise the
  * table at load time; -1 = unset.  The one option read when a network is created (LBC_NO_SIDE_STREAM) applies to
  * networks created afterwards.  An LBC_* environment variable that is not in the table (a switch of an earlier round, a typo) is reported

@@ -83,12 +83,13 @@ class BiasedBirdViewDataset(BirdViewDataset):
 
 
 def get_birdview_device(dataset_dir, batch_size, device, crop_x_jitter=0, crop_y_jitter=0, angle_jitter=0, n_step=5, gap=5, max_frames=None,
-                        cmd_biased=False, samples=(1000, 10), seed=0, rank=0):
+                        cmd_biased=False, samples=(1000, 10), seed=0, rank=0, loader=None):
     """(train, val) DeviceLoaders as reference get_birdview (birdview_lmdb.py:247-285): jitter, frame cap and biased sampling on the
-    training split only; 1000 / 10 random batches per epoch"""
+    training split only; 1000 / 10 random batches per epoch.  loader: another class with DeviceLoader's constructor (resident.ResidentLoader)"""
+    loader = loader or DeviceLoader
     cls = BiasedBirdViewDataset if cmd_biased else BirdViewDataset
     train = cls(str(Path(dataset_dir) / "train"), gap=gap, n_step=n_step, crop_x_jitter=crop_x_jitter, crop_y_jitter=crop_y_jitter,
                 angle_jitter=angle_jitter, max_frames=max_frames)
     val = BirdViewDataset(str(Path(dataset_dir) / "val"), gap=gap, n_step=n_step, crop_x_jitter=0, crop_y_jitter=0, angle_jitter=0)
-    return (DeviceLoader(train, batch_size, samples[0], device, seed=seed, rank=rank),
-            DeviceLoader(val, batch_size, samples[1], device, seed=seed + 1, rank=rank))
+    return (loader(train, batch_size, samples[0], device, seed=seed, rank=rank),
+            loader(val, batch_size, samples[1], device, seed=seed + 1, rank=rank))

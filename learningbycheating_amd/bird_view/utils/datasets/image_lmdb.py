@@ -289,12 +289,13 @@ class DeviceLoader:
         self.resume_at = int(sd.get("position", 0))
 
 
-def get_image_device(dataset_dir, batch_size, device, augment=None, n_step=5, gap=5, batch_aug=1, samples=(1000, 10), seed=0, rank=0):
+def get_image_device(dataset_dir, batch_size, device, augment=None, n_step=5, gap=5, batch_aug=1, samples=(1000, 10), seed=0, rank=0, loader=None):
     """(train, val) DeviceLoaders with the reference's epoch definition (1000 / 10 random batches; validation without
-    augmentation or batch_aug: image_lmdb.py:278-281)"""
-    train = DeviceLoader(ImageDataset(str(Path(dataset_dir) / "train"), gap=gap, n_step=n_step, augment_strategy=augment, batch_aug=batch_aug),
-                         batch_size, samples[0], device, augment=augment, batch_aug=batch_aug, seed=seed, rank=rank)
-    val = DeviceLoader(ImageDataset(str(Path(dataset_dir) / "val"), gap=gap, n_step=n_step), batch_size, samples[1], device, seed=seed + 1, rank=rank)
+    augmentation or batch_aug: image_lmdb.py:278-281).  loader: another class with DeviceLoader's constructor (resident.ResidentLoader)"""
+    loader = loader or DeviceLoader
+    train = loader(ImageDataset(str(Path(dataset_dir) / "train"), gap=gap, n_step=n_step, augment_strategy=augment, batch_aug=batch_aug),
+                   batch_size, samples[0], device, augment=augment, batch_aug=batch_aug, seed=seed, rank=rank)
+    val = loader(ImageDataset(str(Path(dataset_dir) / "val"), gap=gap, n_step=n_step), batch_size, samples[1], device, seed=seed + 1, rank=rank)
     return train, val
 
 

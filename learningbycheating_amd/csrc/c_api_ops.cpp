@@ -300,4 +300,23 @@ int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, 
     return lbc_replay_writeback_launch(w_batch, idx, B, reps, n, new_w, (hipStream_t)stream);
 }
 
+// ---- device-resident LMDB dataset ------------------------------------------------------------------------------
+int lbc_dataset_gather_crop_u8(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
+                               unsigned char* dst, lbc_stream_t stream)
+{
+    return lbc_dataset_gather_crop_launch(src, idx, B, reps, SH, SW, C, y0, x0, H, W, dst, (hipStream_t)stream);
+}
+
+int lbc_dataset_gather_warp_crop_u8(const unsigned char* src, const int* draws, const lbc_warp_params* table, int A, int B, int reps, int SH, int SW,
+                                    int C, int H, int W, unsigned char* dst, lbc_stream_t stream)
+{
+    return lbc_dataset_gather_warp_crop_launch(src, draws, reinterpret_cast<const WarpParams*>(table), A, B, reps, SH, SW, C, H, W, dst, (hipStream_t)stream);
+}
+
+int lbc_dataset_targets(const float* table, const int* row_of_sample, const int* draws, int B, int reps, int gap, int n_step, int img_size, int crop_size,
+                        float* loc, float* speed, lbc_stream_t stream)
+{
+    return lbc_dataset_targets_launch(table, row_of_sample, draws, B, reps, gap, n_step, img_size, crop_size, loc, speed, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "lbc_common.hpp"
 #include "lbc_hash.hpp"
 #include "lbc_kernels.hpp"
+#include "lbc_warp.hpp"
 
 namespace {
 
@@ -36,10 +37,8 @@ __global__ __launch_bounds__(256) void crop_u8_k(const unsigned char* __restrict
 
 // Bird-view rotation + crop, one pass: dst[n] = crop(warpAffine(src[n], M_n)) as the reference's privileged-agent loader does per sample
 // on the CPU (bird_view/utils/datasets/birdview_lmdb.py:103-125: cv2.warpAffine(bird_view, cv2.getRotationMatrix2D((160, 260), delta_angle,
-// 1.0), (320, 320), flags=cv2.INTER_LINEAR), then the jittered 192 x 192 window).  The arithmetic restates OpenCV's 8-bit bilinear
-// warpAffine (imgwarp.cpp, remap with INTER_BITS = 5): source coordinates in 1/1024 fixed point from the INVERTED matrix (rounded half to
-// even like cvRound, + 16, >> 5 -> 1/32 pixel), a 32 x 32 table of 15-bit weights whose four entries sum to 32768,
-// (sum + 16384) >> 15, zero outside the image (BORDER_CONSTANT).
+// 1.0), (320, 320), flags=cv2.INTER_LINEAR), then the jittered 192 x 192 window).  The per-pixel arithmetic (OpenCV's 8-bit bilinear
+// warpAffine restated) is lbc_warp_pixel_u8 of lbc_warp.hpp, shared with the indexed form in dataset.hip.
 // p.im = the inverted matrix (iM0, iM1, b1, iM3, iM4, b2) in double, p.y0 / p.x0 the window origin in the warped image.
 __global__ __launch_bounds__(256) void warp_crop_u8_k(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, const WarpParams* __restrict__ params,
                                                       int N, int SH, int SW, int C, int H, int W)
@@ -51,27 +50,7 @@ __global__ __launch_bounds__(256) void warp_crop_u8_k(const unsigned char* __res
         const int pix = (int)(i - (long long)n * H * W);
         const WarpParams p = params[n];
         const int y = p.y0 + pix / W, x = p.x0 + pix % W;
-        const int adelta = (int)rint(p.im[0] * x * 1024.0), bdelta = (int)rint(p.im[3] * x * 1024.0);
-        const int X0 = (int)rint((p.im[1] * y + p.im[2]) * 1024.0) + 16, Y0 = (int)rint((p.im[4] * y + p.im[5]) * 1024.0) + 16;
-        const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-        const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
-        // the weights of table entry (fy, fx)
-        const float ax = (float)fx * (1.f / 32.f), ay = (float)fy * (1.f / 32.f);
-        const float wf[4] = {(1.f - ay) * (1.f - ax), (1.f - ay) * ax, ay * (1.f - ax), ay * ax};
-        // (bilinear weights are products of two multiples of 1/32: every w[k] is an exact multiple of 32 and the four sum to 32768
-        //  exactly -- OpenCV's fix-up of the table sum can never fire for INTER_LINEAR, it is not restated)
-        int w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = (int)rintf(wf[k] * 32768.f);
-        const bool in00 = (unsigned)sy < (unsigned)SH && (unsigned)sx < (unsigned)SW, in01 = (unsigned)sy < (unsigned)SH && (unsigned)(sx + 1) < (unsigned)SW;
-        const bool in10 = (unsigned)(sy + 1) < (unsigned)SH && (unsigned)sx < (unsigned)SW, in11 = (unsigned)(sy + 1) < (unsigned)SH && (unsigned)(sx + 1) < (unsigned)SW;
-        const unsigned char* s0 = src + (((long long)n * SH + sy) * SW + sx) * C;
-        unsigned char* d = dst + i * C;
-        for (int c = 0; c < C; ++c) {
-            const int v00 = in00 ? s0[c] : 0, v01 = in01 ? s0[C + c] : 0, v10 = in10 ? s0[(long long)SW * C + c] : 0, v11 = in11 ? s0[(long long)SW * C + C + c] : 0;
-            const int v = (v00 * w[0] + v01 * w[1] + v10 * w[2] + v11 * w[3] + (1 << 14)) >> 15;
-            d[c] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
+        lbc_warp_pixel_u8(src + (long long)n * SH * SW * C, dst + i * C, p.im, y, x, SH, SW, C);
     }
 }
 

@@ -245,7 +245,15 @@ int lbc_replay_scatter_launch(const unsigned char* src, long long row_bytes, con
 int lbc_replay_meta_launch(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, hipStream_t s);
 int lbc_replay_writeback_launch(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, hipStream_t s);
 
-// ---- losses (phase 0 / phase 1 / bird-view) -------------------------------------------
+// ---- device-resident LMDB dataset (dataset.hip) ------------------------------------------------------------
+int lbc_dataset_gather_crop_launch(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
+                                   unsigned char* dst, hipStream_t s);
+int lbc_dataset_gather_warp_crop_launch(const unsigned char* src, const int* draws, const WarpParams* table, int A, int B, int reps, int SH, int SW, int C,
+                                        int H, int W, unsigned char* dst, hipStream_t s);
+int lbc_dataset_targets_launch(const float* table, const int* row_of_sample, const int* draws, int B, int reps, int gap, int n_step, int img_size,
+                               int crop_size, float* loc, float* speed, hipStream_t s);
+
+// ---- losses (phase 0 / phase 1 / bird-view)-------------------------------------------
 struct LossArgs {
     const float* pred;           // student output, normalised [-1,1]
     const float* target;         // teacher output / targets

@@ -1,5 +1,6 @@
 """Train / validation batch sources of the training scripts: the LMDB dataset (--dataset_dir, reference
-bird_view/utils/datasets/image_lmdb.py:270-293 get_image) or device-resident synthetic frames (--synthetic N).  Both hand out
+bird_view/utils/datasets/image_lmdb.py:270-293 get_image; with --resident read once and kept in HBM, bird_view/utils/datasets/resident.py)
+or device-resident synthetic frames (--synthetic N).  All hand out
 the dataset's uint8 frames on the device: (rgb u8 (B,160,384,3), birdview u8 (B,192,192,7), location (B,5,2), command (B,) on
 the host, speed (B,)); the colour augmentation (--augment) and --batch_aug run on the GPU for either source."""
 import torch
@@ -61,6 +62,11 @@ def make_loaders(config, device, rank=0, world=1):
     val_iters = max(1, iters // 100)
     augment, batch_aug = da.get("augment"), int(da.get("batch_aug", 1) or 1)
     if da.get("dataset_dir"):
+        loader = None
+        if da.get("resident"):               # --resident: the whole dataset in HBM, both splits (it raises when they do not fit)
+            import functools
+            from ..bird_view.utils.datasets.resident import ResidentLoader
+            loader = functools.partial(ResidentLoader, reserve_gb=da.get("resident_reserve_gb"))
         if any(k in da for k in ("crop_x_jitter", "crop_y_jitter", "angle_jitter", "cmd_biased", "max_frames")):
             # train_birdview's loader (reference bird_view/utils/datasets/birdview_lmdb.py:247-285): rotation / window jitter with the
             # waypoints following, command-biased sampling, a frame cap -- the rotation runs on the GPU (lbc_birdview_warp_crop_u8)
@@ -68,10 +74,10 @@ def make_loaders(config, device, rank=0, world=1):
             return get_birdview_device(da["dataset_dir"], bs, device, crop_x_jitter=da.get("crop_x_jitter", 0) or 0,
                                        crop_y_jitter=da.get("crop_y_jitter", 0) or 0, angle_jitter=da.get("angle_jitter", 0) or 0,
                                        n_step=da.get("n_step", 5), gap=da.get("gap", 5), max_frames=da.get("max_frames"),
-                                       cmd_biased=bool(da.get("cmd_biased")), samples=(iters, val_iters), seed=0, rank=rank)
+                                       cmd_biased=bool(da.get("cmd_biased")), samples=(iters, val_iters), seed=0, rank=rank, loader=loader)
         from ..bird_view.utils.datasets.image_lmdb import get_image_device
         return get_image_device(da["dataset_dir"], bs, device, augment=augment, n_step=da.get("n_step", 5), gap=da.get("gap", 5),
-                                batch_aug=batch_aug, samples=(iters, val_iters), seed=0, rank=rank)
+                                batch_aug=batch_aug, samples=(iters, val_iters), seed=0, rank=rank, loader=loader)
     train = SyntheticFrames(config["synthetic"], device, seed=0, rank=rank, world=world)
     val = SyntheticFrames(max(bs, config["synthetic"] // 8), device, seed=1, rank=rank, world=world)
     return (_SyntheticLoader(train, bs, iters, augment, batch_aug, seed=rank), _SyntheticLoader(val, bs, val_iters))

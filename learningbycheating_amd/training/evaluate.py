@@ -14,6 +14,7 @@ import torch
 from ..bird_view.models.birdview import BirdViewPolicyModelSS
 from ..bird_view.models.image import ImagePolicyModelSS
 from ..bird_view.utils.train_utils import one_hot
+from . import resume
 from .data import make_loaders
 from .native import NativeTrainer, camera_struct
 
@@ -69,7 +70,9 @@ def main(argv=None):
     parser.add_argument("--batches", type=int, default=10, help="validation batches (the training scripts' pass has iters_per_epoch / 100)")
     parser.add_argument("--fixed_offset", type=float, default=4.0)
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32")
+    resume.add_resident_arguments(parser)
     parsed = parser.parse_args(argv)
+    resident = resume.resident_entries(parsed)
     if not torch.cuda.is_available():
         raise SystemExit("evaluation needs a ROCm GPU")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -79,6 +82,7 @@ def main(argv=None):
     data_args = {"dataset_dir": parsed.dataset_dir, "batch_size": parsed.batch_size, "n_step": 5, "gap": 5}
     if phase == "birdview" and parsed.dataset_dir:
         data_args.update(crop_x_jitter=0, crop_y_jitter=0, angle_jitter=0)
+    data_args.update(resident)
     config = {"data_args": data_args, "synthetic": parsed.synthetic, "iters_per_epoch": 100 * int(parsed.batches)}
     _, data_val = make_loaders(config, device)
     res = validation_pass(trainer, data_val, device).result()

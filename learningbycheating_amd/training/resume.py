@@ -1,5 +1,5 @@
 """What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate /
---lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics.
+--lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics / --resident.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -32,6 +32,32 @@ def add_arguments(parser, with_resume=True):
     add_accumulate_argument(parser)
     add_recipe_arguments(parser)
     add_metrics_arguments(parser)
+    add_resident_arguments(parser)
+
+
+def add_resident_arguments(parser):
+    parser.add_argument("--resident", action="store_true",
+                        help="with --dataset_dir: read the whole dataset once and keep it on the GPU (ResidentLoader); every batch is then "
+                             "gathered, cropped / rotated and given its waypoints by kernels, the host only draws indices.  The batches are "
+                             "the ones the host loader hands out.  Fails when the dataset does not fit.  Default: off")
+    parser.add_argument("--resident-reserve-gb", type=float, default=None, metavar="GB",
+                        help="with --resident: device memory to leave free for networks and workspaces (default: what batch 256 in fp32 needs)")
+
+
+def resident_entries(parsed):
+    """data_args entries of --resident / --resident-reserve-gb; a run without them writes the config.json it always wrote"""
+    if not getattr(parsed, "resident", False):
+        if getattr(parsed, "resident_reserve_gb", None) is not None:
+            raise SystemExit("--resident-reserve-gb needs --resident")
+        return {}
+    if not parsed.dataset_dir:
+        raise SystemExit("--resident needs --dataset_dir (synthetic frames already live on the device)")
+    out = {"resident": True}
+    if parsed.resident_reserve_gb is not None:
+        if parsed.resident_reserve_gb < 0:
+            raise SystemExit("--resident-reserve-gb must not be negative")
+        out["resident_reserve_gb"] = float(parsed.resident_reserve_gb)
+    return out
 
 
 def add_metrics_arguments(parser):

@@ -189,6 +189,7 @@ def main(argv=None):
         "synthetic": parsed.synthetic, "iters_per_epoch": parsed.iters_per_epoch, "rank": rank, "world_size": world,
     }
     config.update(resume.config_entries(parsed))
+    config["data_args"].update(resume.resident_entries(parsed))
     train(config)
     if world > 1:
         dist.destroy_process_group()
