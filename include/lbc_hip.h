@@ -572,13 +572,19 @@ int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, 
  *   the measurement table [rows][5] f32 = (x, y, heading, speed, cmd), one row per stored frame, episodes contiguous; the sample's row
  *   is row_of_sample[idx], its k-th future position row + (k + 1) * gap (the caller guarantees that these rows belong to the same
  *   episode).  Restates the reference's image_lmdb.py:143-163 / birdview_lmdb.py:127-141: (x - ox) * 5 in f32, angle = heading +
- *   delta_angle * pi / 180 and everything after it in double, one cast to f32 at the end. */
+ *   delta_angle * pi / 180 and everything after it in double, one cast to f32 at the end.
+ * lbc_dataset_gather_rows_f32: dst[(b * reps + r) * R + j] = src[draws[b * stride] * R + j], j < R: an indexed gather of f32 rows (the
+ *   cached waypoints of the frozen teacher, R = 50: all 4 x 5 x 2, then the selected 5 x 2).  stride = 4 reads the frame index out of
+ *   the records above, stride = 1 a dense int32 index vector.  Moves 8 bytes per lane when R is even and both base pointers are
+ *   multiples of 8 (200-byte rows are 8-byte aligned, not 16), 4 bytes per lane otherwise.  The words move as integers: NaN payloads,
+ *   infinities and -0.0 arrive bit for bit.  No atomics; every launch writes the same bytes. */
 int lbc_dataset_gather_crop_u8(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
                                unsigned char* dst, lbc_stream_t stream);
 int lbc_dataset_gather_warp_crop_u8(const unsigned char* src, const int* draws, const lbc_warp_params* table, int A, int B, int reps, int SH, int SW,
                                     int C, int H, int W, unsigned char* dst, lbc_stream_t stream);
 int lbc_dataset_targets(const float* table, const int* row_of_sample, const int* draws, int B, int reps, int gap, int n_step, int img_size, int crop_size,
                         float* loc, float* speed, lbc_stream_t stream);
+int lbc_dataset_gather_rows_f32(const float* src, const int* draws, int stride, int B, int reps, int R, float* dst, lbc_stream_t stream);
 
 /* Runtime options (A/B switches, tuning knobs, test hooks): names are the LBC_* environment variables that initialise the
  * table at load time; -1 = unset.  The one option read when a network is created (LBC_NO_SIDE_STREAM) applies to

@@ -184,6 +184,7 @@ _SIGNATURES = {
     "lbc_dataset_gather_crop_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p]),
     "lbc_dataset_gather_warp_crop_u8": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
     "lbc_dataset_targets": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p]),
+    "lbc_dataset_gather_rows_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "lbc_config_set": (c_int, [c_char_p, ctypes.c_longlong]),
     "lbc_config_get": (ctypes.c_longlong, [c_char_p]),
     "lbc_profile_enable": (c_int, [c_int]),

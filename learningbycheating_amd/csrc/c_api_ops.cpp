@@ -319,4 +319,9 @@ int lbc_dataset_targets(const float* table, const int* row_of_sample, const int*
     return lbc_dataset_targets_launch(table, row_of_sample, draws, B, reps, gap, n_step, img_size, crop_size, loc, speed, (hipStream_t)stream);
 }
 
+int lbc_dataset_gather_rows_f32(const float* src, const int* draws, int stride, int B, int reps, int R, float* dst, lbc_stream_t stream)
+{
+    return lbc_dataset_gather_rows_launch(src, draws, stride, B, reps, R, dst, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -11,6 +11,8 @@
 //                      origin follows (dx, dy).  The pixel is lbc_warp_pixel_u8, the function warp_crop_u8_k calls.
 //   targets            ImageDataset.raw()'s waypoints and speed, one lane per sample, from the measurement table (x, y, heading, speed,
 //                      cmd as f32, one row per stored frame, episodes contiguous): the future positions are rows row + k * gap.
+//   gather_rows        dst row b * reps + r = src row draws[b * stride] for f32 rows: the cached waypoints of the frozen teacher
+//                      (--cache-teacher, 50 floats per frame) through the record (stride 4) or a dense index vector (stride 1).
 // Every offset is 64-bit: 2,996 stored maps pass 2^31 bytes.
 #include "lbc_common.hpp"
 #include "lbc_kernels.hpp"
@@ -114,6 +116,22 @@ __global__ __launch_bounds__(256) void targets_k(const float* __restrict__ table
     }
 }
 
+// Row copy through an index: word i of output row (b * reps + r) = word i of source row draws[b * stride], rows of W words of type T
+// (uint2: the cached teacher rows are 200 bytes, which 8 divides and 16 does not; unsigned: odd rows and bases that are not 8-byte
+// aligned).  Integer words, so a NaN's payload and the sign of a zero pass through untouched.
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_k(const T* __restrict__ src, const int* __restrict__ draws, int stride, long long rows, int reps,
+                                                     int W, T* __restrict__ dst)
+{
+    const long long total = rows * W;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const long long row = i / W;
+        const int j = (int)(i - row * W);
+        dst[i] = src[(long long)draws[(row / reps) * stride] * W + j];
+    }
+}
+
 int grid_1d(long long total)
 {
     long long b = (total + 255) / 256;
@@ -178,4 +196,21 @@ int lbc_dataset_targets_launch(const float* table, const int* row_of_sample, con
     hipLaunchKernelGGL(targets_k, dim3((unsigned)lbc_cdiv(B, 256)), dim3(256), 0, s, table, row_of_sample, reinterpret_cast<const Draw*>(draws), B, reps, gap,
                        n_step, img_size, crop_size, loc, speed);
     return lbc_check_launch("dataset_targets");
+}
+
+int lbc_dataset_gather_rows_launch(const float* src, const int* draws, int stride, int B, int reps, int R, float* dst, hipStream_t s)
+{
+    LBC_REQUIRE(src && draws && dst, "dataset_gather_rows_f32: null argument");
+    LBC_REQUIRE(B >= 1 && reps >= 1 && R >= 1 && stride >= 1, "dataset_gather_rows_f32: B = %d, reps = %d, R = %d, stride = %d, all must be positive", B,
+                reps, R, stride);
+    const long long rows = (long long)B * reps;
+    LbcProfScope prof("dataset_gather_rows_f32", 0.0, 8.0 * (double)rows * R, s);
+    const bool pairs = R % 2 == 0 && (reinterpret_cast<uintptr_t>(src) & 7) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0;
+    if (pairs)
+        hipLaunchKernelGGL(gather_rows_k<uint2>, dim3((unsigned)grid_1d(rows * (R / 2))), dim3(256), 0, s, reinterpret_cast<const uint2*>(src), draws, stride,
+                           rows, reps, R / 2, reinterpret_cast<uint2*>(dst));
+    else
+        hipLaunchKernelGGL(gather_rows_k<unsigned>, dim3((unsigned)grid_1d(rows * R)), dim3(256), 0, s, reinterpret_cast<const unsigned*>(src), draws, stride,
+                           rows, reps, R, reinterpret_cast<unsigned*>(dst));
+    return lbc_check_launch("dataset_gather_rows_f32");
 }

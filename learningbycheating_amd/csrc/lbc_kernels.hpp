@@ -252,6 +252,7 @@ int lbc_dataset_gather_warp_crop_launch(const unsigned char* src, const int* dra
                                         int H, int W, unsigned char* dst, hipStream_t s);
 int lbc_dataset_targets_launch(const float* table, const int* row_of_sample, const int* draws, int B, int reps, int gap, int n_step, int img_size,
                                int crop_size, float* loc, float* speed, hipStream_t s);
+int lbc_dataset_gather_rows_launch(const float* src, const int* draws, int stride, int B, int reps, int R, float* dst, hipStream_t s);
 
 // ---- losses (phase 0 / phase 1 / bird-view)-------------------------------------------
 struct LossArgs {

@@ -55,18 +55,24 @@ class _SyntheticLoader:
             self.aug.load_state_dict(sd["aug"])
 
 
-def make_loaders(config, device, rank=0, world=1):
-    """-> (train, val): iterables of batches; one pass = one epoch (reference: 1000 train + 10 validation batches)"""
+def make_loaders(config, device, rank=0, world=1, teacher=None):
+    """-> (train, val): iterables of batches; one pass = one epoch (reference: 1000 train + 10 validation batches).
+    teacher: the frozen privileged agent, for data_args["cache_teacher"] (--cache-teacher): both splits then hand out its cached
+    waypoints in the bird-view's place (every rank builds its own caches: every rank holds both splits whole)"""
     da = config["data_args"]
     bs, iters = da["batch_size"], int(config["iters_per_epoch"])
     val_iters = max(1, iters // 100)
     augment, batch_aug = da.get("augment"), int(da.get("batch_aug", 1) or 1)
+    if da.get("cache_teacher") and not (da.get("dataset_dir") and da.get("resident") and teacher is not None):
+        raise ValueError("make_loaders: cache_teacher needs dataset_dir, resident and the teacher")
     if da.get("dataset_dir"):
         loader = None
         if da.get("resident"):               # --resident: the whole dataset in HBM, both splits (it raises when they do not fit)
             import functools
             from ..bird_view.utils.datasets.resident import ResidentLoader
             loader = functools.partial(ResidentLoader, reserve_gb=da.get("resident_reserve_gb"))
+            if da.get("cache_teacher"):
+                loader = functools.partial(loader, teacher=teacher)
         if any(k in da for k in ("crop_x_jitter", "crop_y_jitter", "angle_jitter", "cmd_biased", "max_frames")):
             # train_birdview's loader (reference bird_view/utils/datasets/birdview_lmdb.py:247-285): rotation / window jitter with the
             # waypoints following, command-biased sampling, a frame cap -- the rotation runs on the GPU (lbc_birdview_warp_crop_u8)

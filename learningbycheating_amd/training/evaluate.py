@@ -32,12 +32,12 @@ def validation_pass(trainer, data, device, metrics=None, max_batches=None):
         if trainer.phase == "birdview":
             trainer.step(birdview, speed, command, target=location.float().contiguous(), update=False, train_mode=False, metrics=m)
         else:
-            trainer.step(rgb_image, speed, command, birdview=birdview, update=False, train_mode=False, metrics=m)
+            trainer.step(rgb_image, speed, command, update=False, train_mode=False, metrics=m, **resume.teacher_arguments(birdview))
     return m
 
 
-def build_trainer(phase, model_path, teacher_path, batch_size, precision, device, fixed_offset=4.0):
-    """the networks and the trainer of `phase` as the training script of that phase builds them, the student loaded from model_path"""
+def build_networks(phase, model_path, teacher_path, precision, device):
+    """-> (student loaded from model_path, frozen teacher or None) as the training script of `phase` builds them"""
     if phase == "birdview":
         net = BirdViewPolicyModelSS("resnet18").to(device)
         teacher = None
@@ -55,6 +55,13 @@ def build_trainer(phase, model_path, teacher_path, batch_size, precision, device
     net.precision = precision
     net.load_state_dict(torch.load(model_path, map_location=device))
     net.eval()
+    return net, teacher
+
+
+def build_trainer(phase, model_path, teacher_path, batch_size, precision, device, fixed_offset=4.0, networks=None):
+    """the networks and the trainer of `phase` as the training script of that phase builds them, the student loaded from model_path.
+    networks: (student, teacher) built before; a teacher of None in phase 0 / 1 gives a trainer without a teacher engine (--cache-teacher)"""
+    net, teacher = networks if networks is not None else build_networks(phase, model_path, teacher_path, precision, device)
     shape = (7, 192, 192) if phase == "birdview" else (3, 160, 384)
     return NativeTrainer(net, teacher, batch_size, shape, device, phase=phase, camera=camera_struct(fixed_offset=float(fixed_offset)))
 
@@ -72,19 +79,21 @@ def main(argv=None):
     parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32")
     resume.add_resident_arguments(parser)
     parsed = parser.parse_args(argv)
-    resident = resume.resident_entries(parsed)
+    resident = resume.resident_entries(parsed, teacher=parsed.phase != "birdview")
     if not torch.cuda.is_available():
         raise SystemExit("evaluation needs a ROCm GPU")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
     phase = PHASES[parsed.phase]
-    trainer = build_trainer(phase, parsed.model_path, parsed.teacher_path, parsed.batch_size, parsed.precision, device, parsed.fixed_offset)
+    net, teacher = build_networks(phase, parsed.model_path, parsed.teacher_path, parsed.precision, device)
     data_args = {"dataset_dir": parsed.dataset_dir, "batch_size": parsed.batch_size, "n_step": 5, "gap": 5}
     if phase == "birdview" and parsed.dataset_dir:
         data_args.update(crop_x_jitter=0, crop_y_jitter=0, angle_jitter=0)
     data_args.update(resident)
     config = {"data_args": data_args, "synthetic": parsed.synthetic, "iters_per_epoch": 100 * int(parsed.batches)}
-    _, data_val = make_loaders(config, device)
+    _, data_val = make_loaders(config, device, teacher=teacher)      # (--cache-teacher: the loaders run the teacher, once per frame)
+    trainer = build_trainer(phase, parsed.model_path, parsed.teacher_path, parsed.batch_size, parsed.precision, device, parsed.fixed_offset,
+                            networks=(net, resume.teacher_for_trainer(config, teacher)))
     res = validation_pass(trainer, data_val, device).result()
     res.update(model_path=str(parsed.model_path), phase=parsed.phase, precision=parsed.precision)
     res["within"] = {"%g" % k: v for k, v in res["within"].items()}

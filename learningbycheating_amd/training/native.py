@@ -72,6 +72,12 @@ class NativeTrainer:
     non-updating steps, in train and eval mode, and never syncs.  `make_metrics()` builds an object that fits this trainer's phase;
     one whose frame (or, for bird-view, target scale / shift) does not fit is refused with ValueError before anything is launched.
 
+    step(..., teacher_out=(sel, all)) (phases 0 and 1): the frozen teacher's waypoints, computed before -- per frame of the dataset by
+    ResidentLoader's teacher cache -- take the place of the teacher's forward: nothing of the teacher is launched and the side stream
+    is not touched.  teacher=None in phase 0 / 1 builds a trainer without a teacher engine (no workspace, no side stream) whose every
+    step needs teacher_out; birdview= and teacher_out= together, or a teacher_out of the wrong shape, dtype or device, are refused with
+    ValueError before anything is launched.
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
@@ -167,11 +173,33 @@ class NativeTrainer:
             raise ValueError("NativeTrainer.step: phase %r compares against target * %r + %r, the metrics object was built for target * %r + %r"
                              % (self.phase, scale, shift, metrics.target_scale, metrics.target_shift))
 
-    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None, metrics=None):
+    def _check_teacher_out(self, teacher_out, birdview, n, device):
+        """the refusals of step(teacher_out=...), before anything is launched -> (sel, all), the one this phase's loss reads packed"""
+        if self.phase not in (0, 1):
+            raise ValueError("NativeTrainer.step: teacher_out is for phases 0 and 1, this trainer runs phase %r" % (self.phase,))
+        if birdview is not None:
+            raise ValueError("NativeTrainer.step: birdview= and teacher_out= together: the teacher's waypoints are either computed or given")
+        try:
+            sel, every = teacher_out
+        except (TypeError, ValueError):
+            raise ValueError("NativeTrainer.step: teacher_out must be a pair (sel, all)") from None
+        for name, t, shape in (("sel", sel, (n, 5, 2)), ("all", every, (n, 4, 5, 2))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != device:
+                raise ValueError("NativeTrainer.step: teacher_out.%s must be a float32 tensor of shape %s on %s, got %s"
+                                 % (name, shape, device, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor)
+                                    else type(t).__name__))
+        # (the loss takes a raw pointer to dense rows: the views a loader's teacher cache hands out have the cached row's pitch)
+        return (sel, every.contiguous()) if self.phase == 1 else (sel.contiguous(), every)
+
+    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None, metrics=None, teacher_out=None):
         """x: student input, float32 (N,C,H,W) in [0,1] or the dataset's uint8 (N,H,W,C) frames; command one-hot (N,4);
         returns the per-sample loss (device tensor).  update=False: forward + loss only.  train_mode=False: the student runs
         in eval mode (running statistics, no buffer update) -- the reference's validation pass (train_image_phase1.py:162-165,256).
-        on_forward (parity tests): called with the trainer after the student's forward, before the loss and the backward."""
+        on_forward (parity tests): called with the trainer after the student's forward, before the loss and the backward.
+        teacher_out=(sel, all) (phases 0 and 1, instead of birdview=): the frozen teacher's waypoints for this batch, float32 (N,5,2)
+        and (N,4,5,2), computed earlier (ResidentLoader's teacher cache).  No teacher forward is launched and no side stream is
+        involved; loss, metrics and `last_teacher` see these tensors where they see the forward's.  A trainer built with teacher=None
+        has no teacher engine and takes every phase-0 / phase-1 step this way."""
         if not train_mode and update:
             raise ValueError("an eval-mode step cannot update (backward through running-statistics BatchNorm is not implemented)")
         if update and self._in_ema_weights:
@@ -179,19 +207,27 @@ class NativeTrainer:
         if metrics is not None:
             self._check_metrics(metrics)
         n = x.shape[0]
+        if teacher_out is not None:
+            teacher_out = self._check_teacher_out(teacher_out, birdview, n, x.device)
+        elif self.phase in (0, 1) and self.teng is None:
+            raise ValueError("NativeTrainer.step: this trainer was built without a teacher (teacher=None): every step needs teacher_out=(sel, all)")
         # the executor takes raw pointers to dense tensors; a permuted / sliced view is packed first (the reference's
         # nn.Module accepts any strides)
         x, speed, command = x.contiguous(), speed.contiguous(), command.contiguous()
         if birdview is not None:
             birdview = birdview.contiguous()
-        if self.phase in (0, 1):
+        overlapped = False                                       # the teacher's forward runs on the side stream in this step
+        if teacher_out is not None:
+            t_sel, t_all = self.last_teacher = teacher_out
+        elif self.phase in (0, 1):
             if not getattr(self.teng, "_frozen", False):        # (somebody ran the teacher through its module API since: the promise is ours again)
                 self.teng.set_frozen(True)
             v = self._versions(self.teacher)
             if v != self._teacher_versions:                     # the "frozen" teacher was written in place: derive its weight copies again
                 self.teng.invalidate()
                 self._teacher_versions = v
-            if self.side is not None and self.overlap_teacher:
+            overlapped = self.side is not None and self.overlap_teacher
+            if overlapped:
                 main = torch.cuda.current_stream(self.device)
                 self.side.wait_stream(main)                      # inputs (and last step's use of the teacher outputs) are ordered before
                 with torch.cuda.stream(self.side):
@@ -201,7 +237,7 @@ class NativeTrainer:
                 t_sel, t_all = self.teng.forward(birdview, speed, command, False)
             self.last_teacher = (t_sel, t_all)
         p_sel, p_all = self.eng.forward(x, speed, command, bool(train_mode))
-        if self.phase in (0, 1) and self.side is not None and self.overlap_teacher:
+        if overlapped:
             torch.cuda.current_stream(self.device).wait_stream(self.side)      # the loss reads the teacher's waypoints
         self.last_pred = (p_sel, p_all)
         if on_forward is not None:

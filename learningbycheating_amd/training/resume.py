@@ -1,5 +1,5 @@
 """What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate /
---lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics / --resident.
+--lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics / --resident / --cache-teacher.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -42,13 +42,24 @@ def add_resident_arguments(parser):
                              "the ones the host loader hands out.  Fails when the dataset does not fit.  Default: off")
     parser.add_argument("--resident-reserve-gb", type=float, default=None, metavar="GB",
                         help="with --resident: device memory to leave free for networks and workspaces (default: what batch 256 in fp32 needs)")
+    parser.add_argument("--cache-teacher", action="store_true",
+                        help="with --resident, phases 0 and 1: run the frozen teacher once over every frame of both splits while they are "
+                             "loaded and keep its waypoints (200 bytes per frame) instead of the bird-view frames; no teacher forward runs "
+                             "in any step afterwards and no teacher engine is built.  Default: off")
 
 
-def resident_entries(parsed):
-    """data_args entries of --resident / --resident-reserve-gb; a run without them writes the config.json it always wrote"""
+def resident_entries(parsed, teacher=True):
+    """data_args entries of --resident / --resident-reserve-gb / --cache-teacher; a run without them writes the config.json it always
+    wrote.  teacher=False: a script without a frozen teacher (train_birdview), which refuses --cache-teacher"""
+    cache = bool(getattr(parsed, "cache_teacher", False))
+    if cache and not teacher:
+        raise SystemExit("--cache-teacher caches the frozen teacher of phases 0 and 1; this script trains the teacher itself, on a jittered "
+                         "window that is no function of the frame")
     if not getattr(parsed, "resident", False):
         if getattr(parsed, "resident_reserve_gb", None) is not None:
             raise SystemExit("--resident-reserve-gb needs --resident")
+        if cache:
+            raise SystemExit("--cache-teacher needs --resident (the cache is built while the dataset is loaded onto the device)")
         return {}
     if not parsed.dataset_dir:
         raise SystemExit("--resident needs --dataset_dir (synthetic frames already live on the device)")
@@ -57,7 +68,21 @@ def resident_entries(parsed):
         if parsed.resident_reserve_gb < 0:
             raise SystemExit("--resident-reserve-gb must not be negative")
         out["resident_reserve_gb"] = float(parsed.resident_reserve_gb)
+    if cache:
+        out["cache_teacher"] = True
     return out
+
+
+def teacher_for_trainer(config, teacher):
+    """the teacher argument of NativeTrainer: with --cache-teacher the loaders hold the teacher's waypoints and no engine is built"""
+    return None if config["data_args"].get("cache_teacher") else teacher
+
+
+def teacher_arguments(birdview):
+    """slot 1 of a batch as NativeTrainer.step's keywords: the bird-view frames for the teacher's forward, or, from a loader with a
+    teacher cache, the waypoints themselves"""
+    from ..bird_view.utils.datasets.resident import TeacherWaypoints
+    return {"teacher_out": birdview} if isinstance(birdview, TeacherWaypoints) else {"birdview": birdview}
 
 
 def add_metrics_arguments(parser):

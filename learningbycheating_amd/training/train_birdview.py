@@ -120,6 +120,7 @@ def main(argv=None):
                              "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
     resume.add_arguments(parser, with_resume=False)
     parsed = parser.parse_args(argv)
+    resident = resume.resident_entries(parsed, teacher=False)      # (this script trains the teacher: --cache-teacher is refused here)
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         raise SystemExit("training needs a ROCm GPU")
@@ -136,7 +137,7 @@ def main(argv=None):
         "synthetic": parsed.synthetic, "iters_per_epoch": parsed.iters_per_epoch, "rank": rank, "world_size": world,
     }
     config.update(resume.config_entries(parsed))
-    config["data_args"].update(resume.resident_entries(parsed))
+    config["data_args"].update(resident)
     train(config)
     if world > 1:
         dist.destroy_process_group()

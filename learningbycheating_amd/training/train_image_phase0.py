@@ -38,7 +38,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
     sync_free = metrics is not None and not is_train                 # the validation pass with --val-metrics reads nothing back per batch
     for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
         command = one_hot(command).to(config["device"])
-        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train, metrics=metrics)
+        # (--cache-teacher: slot 1 holds the teacher's cached waypoints instead of the frames its forward would read)
+        loss = trainer.step(rgb_image, speed, command, update=update, train_mode=is_train, metrics=metrics, **resume.teacher_arguments(birdview))
         windows.after_step(update)
         if ((i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch) and not sync_free:
             bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
@@ -81,9 +82,9 @@ def train(config):
     broadcast_module(net)
     broadcast_module(teacher_net)
     bs = config["data_args"]["batch_size"]
-    data_train, data_val = make_loaders(config, device, rank, world)
+    data_train, data_val = make_loaders(config, device, rank, world, teacher=teacher_net)
     cam = camera_struct(**{k: float(v) for k, v in config["camera_args"].items()})
-    trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
+    trainer = NativeTrainer(net, resume.teacher_for_trainer(config, teacher_net), bs, (3, 160, 384), device, phase=0, lr=config["optimizer_args"]["lr"], world_size=world, camera=cam,
                             skip_nonfinite=config.get("skip_nonfinite", False),
                             max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
     loaders = {"train": data_train, "val": data_val}

@@ -70,7 +70,8 @@ def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, load
         command = one_hot(command).to(device)
         if is_train and config["speed_noise"] > 0:
             speed = torch.clamp(speed + torch.randn_like(speed) * config["speed_noise"], 0, 10)
-        loss = trainer.step(rgb_image, speed, command, birdview=birdview, update=update, train_mode=is_train, metrics=metrics)
+        # (--cache-teacher: slot 1 holds the teacher's cached waypoints instead of the frames its forward would read)
+        loss = trainer.step(rgb_image, speed, command, update=update, train_mode=is_train, metrics=metrics, **resume.teacher_arguments(birdview))
         windows.after_step(update)
         should_log = (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch
         if should_log and not sync_free:
@@ -123,9 +124,9 @@ def train(config):
     broadcast_module(teacher_net)
 
     bs = config["data_args"]["batch_size"] * int(config["data_args"].get("batch_aug", 1) or 1)
-    data_train, data_val = make_loaders(config, device, rank, world)
+    data_train, data_val = make_loaders(config, device, rank, world, teacher=teacher_net)
     cam = camera_struct(**{k: float(v) for k, v in config["agent_args"]["camera_args"].items()})
-    trainer = NativeTrainer(net, teacher_net, bs, (3, 160, 384), device, phase=1, lr=config["optimizer_args"]["lr"],
+    trainer = NativeTrainer(net, resume.teacher_for_trainer(config, teacher_net), bs, (3, 160, 384), device, phase=1, lr=config["optimizer_args"]["lr"],
                             world_size=world, camera=cam, skip_nonfinite=config.get("skip_nonfinite", False),
                             max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
     loaders = {"train": data_train, "val": data_val}
@@ -190,6 +191,8 @@ def main(argv=None):
     }
     config.update(resume.config_entries(parsed))
     config["data_args"].update(resume.resident_entries(parsed))
+    if config["data_args"].get("cache_teacher") and parsed.speed_noise > 0:
+        raise SystemExit("--cache-teacher with --speed_noise: the live teacher reads the noisy speed, which is no function of the frame")
     train(config)
     if world > 1:
         dist.destroy_process_group()
