@@ -13,8 +13,7 @@ import torch
 
 from ..bird_view.models.birdview import BirdViewPolicyModelSS
 from ..bird_view.models.image import ImagePolicyModelSS
-from ..bird_view.utils.train_utils import one_hot
-from . import resume
+from . import loop, resume
 from .data import make_loaders
 from .native import NativeTrainer, camera_struct
 
@@ -25,14 +24,10 @@ def validation_pass(trainer, data, device, metrics=None, max_batches=None):
     """one pass over `data` without updates, in eval mode, feeding `metrics` (default: a fresh object that fits the trainer's phase);
     nothing is read back inside the loop.  -> the metrics object"""
     m = metrics if metrics is not None else trainer.make_metrics()
-    for i, (rgb_image, birdview, location, command, speed) in enumerate(data):
+    for i, batch in enumerate(data):
         if max_batches is not None and i >= max_batches:
             break
-        command = one_hot(command).to(device)
-        if trainer.phase == "birdview":
-            trainer.step(birdview, speed, command, target=location.float().contiguous(), update=False, train_mode=False, metrics=m)
-        else:
-            trainer.step(rgb_image, speed, command, update=False, train_mode=False, metrics=m, **resume.teacher_arguments(birdview))
+        loop.step_batch(trainer, batch, device, update=False, train_mode=False, metrics=m)
     return m
 
 
@@ -76,14 +71,12 @@ def main(argv=None):
     parser.add_argument("--batch_size", type=int, default=32)
     parser.add_argument("--batches", type=int, default=10, help="validation batches (the training scripts' pass has iters_per_epoch / 100)")
     parser.add_argument("--fixed_offset", type=float, default=4.0)
-    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32")
+    loop.add_precision_argument(parser)
     resume.add_resident_arguments(parser)
     parsed = parser.parse_args(argv)
     resident = resume.resident_entries(parsed, teacher=parsed.phase != "birdview")
-    if not torch.cuda.is_available():
-        raise SystemExit("evaluation needs a ROCm GPU")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(device)
+    _, _, local = loop.ranks()
+    device = loop.select_device(local, "evaluation")
     phase = PHASES[parsed.phase]
     net, teacher = build_networks(phase, parsed.model_path, parsed.teacher_path, parsed.precision, device)
     data_args = {"dataset_dir": parsed.dataset_dir, "batch_size": parsed.batch_size, "n_step": 5, "gap": 5}

@@ -1,5 +1,8 @@
-"""What the training scripts share for --save_state / --resume / --skip-nonfinite / --clip-grad-norm / --log-grad-norm / --accumulate /
---lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics / --resident / --cache-teacher.
+"""The flags, config entries and state files of the options the training scripts share: --save_state / --resume / --skip-nonfinite /
+--clip-grad-norm / --log-grad-norm / --accumulate / --lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics /
+--resident / --cache-teacher.  Every option is declared here once (add_arguments), turned into config entries here (config_entries,
+resident_entries: a run without an option writes the config.json it always wrote) and read back here by what the loop calls on logging
+iterations and at epoch ends.  The loop itself -- the pass over a loader, the epochs, the launch -- is training/loop.py.
 
 `train_state.th` in log_dir holds everything a continued run needs: NativeTrainer.state_dict() (student, optimizer sidecar in
 torch.optim.Adam's format, guard counters), both loaders' states, the last finished epoch and torch's CPU + device RNG states.
@@ -24,15 +27,24 @@ def add_arguments(parser, with_resume=True):
     parser.add_argument("--seed", type=int, default=None,
                         help="seed torch's generators before the networks are built (default: unseeded, as the reference): two runs with "
                              "the same seed and flags start from the same weights")
-    parser.add_argument("--skip-nonfinite", action="store_true",
-                        help="skip (on the device, without a host round trip) every optimizer step whose gradients hold a NaN or an infinity")
-    parser.add_argument("--max-skipped", type=int, default=50,
-                        help="with --skip-nonfinite: abort when more steps than this were skipped in a row (checked on logging iterations)")
+    add_guard_arguments(parser)
     add_clip_arguments(parser)
     add_accumulate_argument(parser)
     add_recipe_arguments(parser)
     add_metrics_arguments(parser)
     add_resident_arguments(parser)
+
+
+def add_guard_arguments(parser):
+    parser.add_argument("--skip-nonfinite", action="store_true",
+                        help="skip (on the device, without a host round trip) every optimizer step whose gradients hold a NaN or an infinity")
+    parser.add_argument("--max-skipped", type=int, default=50,
+                        help="with --skip-nonfinite: abort when more steps than this were skipped in a row (checked on logging iterations)")
+
+
+def guard_entries(parsed):
+    """config entries of --skip-nonfinite / --max-skipped; a run without them writes the config.json it always wrote"""
+    return {"skip_nonfinite": True, "max_skipped": int(parsed.max_skipped)} if parsed.skip_nonfinite else {}
 
 
 def add_resident_arguments(parser):
@@ -208,6 +220,12 @@ def recipe_kwargs(config):
     return {k: config[k] for k in ("lr_schedule", "weight_decay", "ema_decay") if k in config}
 
 
+def trainer_kwargs(config):
+    """NativeTrainer's keywords of the guard, the clip, --accumulate and the entries above"""
+    return dict(skip_nonfinite=config.get("skip_nonfinite", False), max_grad_norm=config.get("max_grad_norm"),
+                accumulate=int(config.get("accumulate", 1)), **recipe_kwargs(config))
+
+
 def log_lr_stats(config, trainer, log_scalar, **tags):
     """on a logging iteration of a run with a schedule / decay / average: lr of the last applied step and, with the average, ema_updates (a sync)"""
     if not recipe_kwargs(config):
@@ -312,8 +330,7 @@ def config_entries(parsed):
         out.update(save_state=True, save_state_every=int(parsed.save_state_every))
     if getattr(parsed, "resume", False):
         out["resume"] = True
-    if parsed.skip_nonfinite:
-        out.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    out.update(guard_entries(parsed))
     out.update(clip_entries(parsed))
     out.update(accumulate_entries(parsed))
     out.update(recipe_entries(parsed))

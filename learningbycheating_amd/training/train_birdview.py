@@ -2,61 +2,25 @@
 BirdViewPolicyModelSS(resnet18) on 7x192x192 maps, L1 (choice='l1', train_birdview.py:161) between the selected
 branch and ground-truth waypoints in pixels."""
 import argparse
-import os
-import time
+import functools
 from pathlib import Path
 
 import torch
-import torch.distributed as dist
 
 from ..bird_view.models.birdview import BirdViewPolicyModelSS
 from ..bird_view.utils import bz_utils as bzu
 from .data import make_loaders
-from ..bird_view.utils.train_utils import one_hot
 from ..parallel import broadcast_module
-from . import resume
+from . import loop, resume
 from .native import NativeTrainer
 
 BACKBONE = "resnet18"
 GAP = 5
 N_STEP = 5
 SAVE_EPOCHS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 384, 512, 768, 1000]
+SPEC = loop.Spec(label="train_birdview", images_per_sec=False, nonfinite=None, save_epochs=SAVE_EPOCHS)
 
-
-def train_or_eval(trainer, data, is_train, config, is_first_epoch, epoch=0, loaders=None):
-    """reference train_birdview.py:102-153"""
-    tick = time.time()
-    update = is_train and not is_first_epoch
-    windows = resume.Windows(config, trainer, getattr(data, "resume_at", 0))        # (--accumulate: iterations stay loader iterations)
-    metrics = resume.pass_metrics(config, trainer, is_train)         # (--val-metrics / --train-metrics; None without them)
-    sync_free = metrics is not None and not is_train                 # the validation pass with --val-metrics reads nothing back per batch
-    for i, (rgb_image, birdview, location, command, speed) in enumerate(data, start=getattr(data, "resume_at", 0)):
-        command = one_hot(command).to(config["device"])
-        loss = trainer.step(birdview, speed, command, target=location.float().contiguous(), update=update, train_mode=is_train, metrics=metrics)
-        windows.after_step(update)
-        if ((i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch) and not sync_free:
-            bzu.log.scalar(is_train=is_train, loss_mean=loss.mean().item())
-            if metrics is not None:
-                resume.log_train_metrics(metrics, bzu.log.scalar)
-            if update:
-                windows.log(bzu.log.scalar, is_train=is_train)
-            skipped = resume.check_skipped(config, trainer, "train_birdview") if is_train else None
-            if skipped is not None:
-                bzu.log.scalar(is_train=is_train, skipped_steps=skipped)
-            if is_train:
-                resume.log_grad_stats(config, trainer, bzu.log.scalar, is_train=is_train)
-                resume.log_lr_stats(config, trainer, bzu.log.scalar, is_train=is_train)
-        now = time.time()
-        bzu.log.scalar(is_train=is_train, fps=1.0 / max(now - tick, 1e-9))
-        tick = now
-        if is_train and not is_first_epoch and loaders is not None:
-            resume.maybe_save_inside_epoch(config, trainer, loaders, epoch, i + 1)
-        if is_first_epoch and i == 10:
-            break
-    if update:
-        windows.end_pass(bzu.log.scalar, is_train=is_train)
-    if sync_free:
-        resume.log_val_metrics(config, metrics, bzu.log.scalar)
+train_or_eval = functools.partial(loop.run_pass, SPEC)        # (reference train_birdview.py:102-153)
 
 
 def train(config):
@@ -75,36 +39,17 @@ def train(config):
     bs = config["data_args"]["batch_size"]
     data_train, data_val = make_loaders(config, device, rank, world)
     trainer = NativeTrainer(net, None, bs, (7, 192, 192), device, phase="birdview", lr=config["optimizer_args"]["lr"], world_size=world,
-                            skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
+                            **resume.trainer_kwargs(config))
     loaders = {"train": data_train, "val": data_val}
     # --resume: the full state (train_state.th: optimizer, loaders, RNG, epoch) when there is one; without it, as before, the newest
     # model-%d.th with a fresh Adam from epoch 0
     state = resume.load(config, trainer, loaders) if full_state else None
-    for epoch in range(state["epoch"] + 1 if state else 0, int(config["max_epoch"]) + 1):
-        net.train()
-        train_or_eval(trainer, data_train, True, config, epoch == 0, epoch, loaders)
-        net.eval()                              # reference train_birdview.py:175-176: validation pass after every epoch
-        with resume.ema_eval(config, trainer):       # (--ema-eval: the validation pass sees the averaged weights)
-            train_or_eval(trainer, data_val, False, config, epoch == 0)
-        net.train()
-        if epoch in SAVE_EPOCHS and rank == 0:
-            torch.save(net.state_dict(), str(Path(config["log_dir"]) / ("model-%d.th" % epoch)))
-            resume.save_ema_model(config, trainer, epoch)
-        rec = bzu.log.end_epoch()
-        if rank == 0:
-            print(rec)
-        resume.save(config, trainer, loaders, epoch)
-    return net
+    return loop.run_epochs(SPEC, config, net, trainer, loaders, state)
 
 
-def main(argv=None):
+def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
-    parser.add_argument("--log_dir", required=True)
-    parser.add_argument("--log_iterations", default=1000)
-    parser.add_argument("--max_epoch", default=1000)
-    parser.add_argument("--dataset_dir", default=None)
-    parser.add_argument("--batch_size", type=int, default=256)
+    loop.add_common_arguments(parser, max_epoch=1000, batch_size=256)
     parser.add_argument("--x_jitter", type=int, default=5)
     parser.add_argument("--y_jitter", type=int, default=0)
     parser.add_argument("--angle_jitter", type=int, default=5)
@@ -112,24 +57,15 @@ def main(argv=None):
     parser.add_argument("--max_frames", type=int, default=None)
     parser.add_argument("--cmd-biased", action="store_true")
     parser.add_argument("--resume", action="store_true")
-    parser.add_argument("--lr", type=float, default=1e-4)
-    parser.add_argument("--synthetic", type=int, default=2048)
-    parser.add_argument("--iters_per_epoch", type=int, default=1000)
-    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
-                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
-                             "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
     resume.add_arguments(parser, with_resume=False)
-    parsed = parser.parse_args(argv)
+    return parser.parse_args(argv)
+
+
+def build_config(parsed, rank, world, device):
     resident = resume.resident_entries(parsed, teacher=False)      # (this script trains the teacher: --cache-teacher is refused here)
-    world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise SystemExit("training needs a ROCm GPU")
-    torch.cuda.set_device(local)
-    if world > 1:
-        dist.init_process_group("nccl")
     config = {
         "log_dir": parsed.log_dir, "log_iterations": parsed.log_iterations, "max_epoch": parsed.max_epoch,
-        "device": torch.device("cuda", local), "precision": parsed.precision, "optimizer_args": {"lr": parsed.lr}, "resume": parsed.resume,
+        "device": device, "precision": parsed.precision, "optimizer_args": {"lr": parsed.lr}, "resume": parsed.resume,
         "data_args": {"dataset_dir": parsed.dataset_dir, "batch_size": parsed.batch_size, "n_step": N_STEP, "gap": parsed.gap,
                       "crop_x_jitter": parsed.x_jitter, "crop_y_jitter": parsed.y_jitter, "angle_jitter": parsed.angle_jitter,
                       "max_frames": parsed.max_frames, "cmd_biased": parsed.cmd_biased},
@@ -138,9 +74,11 @@ def main(argv=None):
     }
     config.update(resume.config_entries(parsed))
     config["data_args"].update(resident)
-    train(config)
-    if world > 1:
-        dist.destroy_process_group()
+    return config
+
+
+def main(argv=None):
+    loop.launch(parse_arguments(argv), build_config, train)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,6 @@ log_dir/train_state.th after every epoch (student, buffer state, augmenter strea
 the next epoch bit for bit."""
 import argparse
 import ctypes
-import os
 import time
 from pathlib import Path
 
@@ -29,7 +28,7 @@ from ..bird_view.utils import bz_utils as bzu
 from ..bird_view.utils.train_utils import one_hot
 from ..optim import FusedAdam
 from ..parallel import broadcast_module
-from . import resume
+from . import loop, resume
 from .native import NativeTrainer, camera_struct
 from .phase2_utils import ReplayBuffer
 from .replay import DeviceReplayBuffer
@@ -70,12 +69,9 @@ def _recipe(config):
 
 def _log_guard(trainer, config):
     """on a logging iteration: skipped_steps (and the abort on a run of them), grad_norm / clip_coef / clipped_steps"""
-    if config.get("skip_nonfinite"):
-        total, row = trainer.skipped()
-        bzu.log.scalar(skipped_steps=total)
-        if row > config["max_skipped"]:
-            raise FloatingPointError("phase 2: %d optimizer steps in a row had non-finite gradients (--max-skipped %d)"
-                                     % (row, config["max_skipped"]))
+    skipped = resume.check_skipped(config, trainer, "phase 2")
+    if skipped is not None:
+        bzu.log.scalar(skipped_steps=skipped)
     resume.log_grad_stats(config, trainer, bzu.log.scalar)
     resume.log_lr_stats(config, trainer, bzu.log.scalar)
 
@@ -257,9 +253,7 @@ def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start
         torch.save(net.state_dict(), str(Path(config["log_dir"]) / ("model-%d.th" % episode)))
 
 
-def main(argv=None, on_epoch_end=None):
-    """on_epoch_end(episode, epoch, replay_buffer, trainer), --replay device only: called after every epoch's state is written -- the
-    place of the reference's per-epoch evaluation / visualisation of the highest-weight samples (train_image_phase2.py:229-250)"""
+def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--log_dir", required=True)
     parser.add_argument("--log_iterations", default=100)
@@ -271,12 +265,8 @@ def main(argv=None, on_epoch_end=None):
     parser.add_argument("--speed_noise", type=float, default=0.0)
     parser.add_argument("--lr", type=float, default=1e-4)
     parser.add_argument("--synthetic", type=int, default=20000, help="frames in the synthetic replay buffer")
-    parser.add_argument("--precision", choices=["fp32", "bf16", "bf16_mfma", "bf16x3"], default="fp32",
-                        help="fp32 = the reference arithmetic; bf16 = bf16 MFMA operands + bf16 activation storage, f32 master weights; "
-                             "bf16x3 = split-bf16 convolution operands (f32-accurate), f32 tensors")
-    parser.add_argument("--skip-nonfinite", action="store_true",
-                        help="skip (on the device) every optimizer step whose gradients hold a NaN or an infinity")
-    parser.add_argument("--max-skipped", type=int, default=50, help="with --skip-nonfinite: abort after more skipped steps in a row than this")
+    loop.add_precision_argument(parser)
+    resume.add_guard_arguments(parser)
     resume.add_clip_arguments(parser)
     resume.add_accumulate_argument(parser)
     resume.add_recipe_arguments(parser, per_epoch=True)
@@ -290,12 +280,16 @@ def main(argv=None, on_epoch_end=None):
     parser.add_argument("--save_state", action="store_true", help="with --replay device: write train_state.th after every epoch")
     parser.add_argument("--resume", action="store_true", help="with --replay device: continue from log_dir/train_state.th when there is one")
     parser.add_argument("--seed", type=int, default=None, help="with --replay device: seed torch's generators before the networks are built")
-    parsed = parser.parse_args(argv)
+    return parser.parse_args(argv)
+
+
+def build_config(parsed, rank, world, device):
+    """the checks of the flag line (a bad combination exits here, before anything is built), then the config; --seed is applied here"""
     device_replay = parsed.replay == "device"
     if parsed.ema_decay is not None or parsed.ema_eval:
         raise SystemExit("train_image_phase2: --ema-decay is not available in phase 2: the optimizer is re-created every epoch and the state file "
                          "is this script's own, so the average has nowhere to live yet (train phase 1 with it, or average afterwards)")
-    recipe = resume.recipe_entries(parsed)               # (a bad combination of flags exits here, before anything is built)
+    recipe = resume.recipe_entries(parsed)
     if not device_replay:
         given = [f for f, on in (("--augment", parsed.augment != "None"), ("--batch_aug", parsed.batch_aug != 1), ("--save_state", parsed.save_state),
                                  ("--resume", parsed.resume), ("--seed", parsed.seed is not None)) if on]
@@ -304,26 +298,18 @@ def main(argv=None, on_epoch_end=None):
                              "resumable state)" % (", ".join(given), "s" if len(given) == 1 else ""))
     if parsed.batch_aug < 1:
         raise SystemExit("train_image_phase2: --batch_aug must be at least 1")
-    world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise SystemExit("training needs a ROCm GPU")
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-    if world > 1:
-        dist.init_process_group("nccl")
     config = {"log_dir": parsed.log_dir, "log_iterations": parsed.log_iterations, "epoch_per_episode": int(parsed.epoch_per_episode),
-              "batch_size": parsed.batch_size, "speed_noise": parsed.speed_noise, "device": device, "rank": rank,
+              "batch_size": parsed.batch_size, "speed_noise": parsed.speed_noise, "device": device, "rank": rank, "world_size": world,
               "precision": parsed.precision,
               "model_args": {"model": "image_ss", "backbone": BACKBONE},
               "agent_args": {"camera_args": {"w": 384, "h": 160, "fov": 90, "world_y": 1.4, "fixed_offset": 4.0}}}
-    if parsed.skip_nonfinite:
-        config.update(skip_nonfinite=True, max_skipped=int(parsed.max_skipped))
+    config.update(resume.guard_entries(parsed))
     config.update(resume.clip_entries(parsed))
     config.update(resume.accumulate_entries(parsed))
     config.update(recipe)
     if device_replay:
         config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
-                      world_size=world, synthetic_frames=True)
+                      synthetic_frames=True)
         if parsed.seed is not None:
             torch.manual_seed(parsed.seed)
             config["seed"] = int(parsed.seed)
@@ -331,6 +317,11 @@ def main(argv=None, on_epoch_end=None):
             config["save_state"] = True
         if parsed.resume:
             config["resume"] = True
+    return config
+
+
+def train(config, parsed, on_epoch_end=None):
+    rank, world, device = config["rank"], config["world_size"], config["device"]
     bzu.log.init(parsed.log_dir, rank)
     bzu.log.save_config({k: v for k, v in config.items() if k not in ("rank", "world_size", "synthetic_frames")})
     net = ImagePolicyModelSS(BACKBONE, all_branch=True).to(device)
@@ -343,9 +334,8 @@ def main(argv=None, on_epoch_end=None):
     broadcast_module(net)
     broadcast_module(teacher)
     trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
-                            camera=camera_struct(), skip_nonfinite=config.get("skip_nonfinite", False),
-                            max_grad_norm=config.get("max_grad_norm"), accumulate=int(config.get("accumulate", 1)), **resume.recipe_kwargs(config))
-    if device_replay:
+                            camera=camera_struct(), **resume.trainer_kwargs(config))
+    if config.get("replay") == "device":
         buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
             buf.reseed(parsed.seed * 7919 + rank)
@@ -356,8 +346,6 @@ def main(argv=None, on_epoch_end=None):
             _train_device(buf, trainer, config, episode, aug, epoch0 if episode == episode0 else 0, on_epoch_end)
             if rank == 0:
                 print("episode %d: %.1f s" % (episode, time.time() - t0))
-        if world > 1:
-            dist.destroy_process_group()
         return {"net": net, "buffer": buf, "trainer": trainer}
     buf = synthetic_buffer(parsed.synthetic // world, device, seed=rank)
     for episode in range(int(parsed.max_episode)):
@@ -365,8 +353,13 @@ def main(argv=None, on_epoch_end=None):
         _train(buf, trainer, config, episode)
         if rank == 0:
             print("episode %d: %.1f s" % (episode, time.time() - t0))
-    if world > 1:
-        dist.destroy_process_group()
+
+
+def main(argv=None, on_epoch_end=None):
+    """on_epoch_end(episode, epoch, replay_buffer, trainer), --replay device only: called after every epoch's state is written -- the
+    place of the reference's per-epoch evaluation / visualisation of the highest-weight samples (train_image_phase2.py:229-250)"""
+    parsed = parse_arguments(argv)
+    return loop.launch(parsed, build_config, lambda config: train(config, parsed, on_epoch_end))
 
 
 if __name__ == "__main__":

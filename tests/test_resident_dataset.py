@@ -309,10 +309,14 @@ def test_flags_and_make_loaders(env, dataset_dir):
         with pytest.raises(SystemExit):
             resume.resident_entries(parser.parse_args(bad))
     from learningbycheating_amd.training import evaluate, train_birdview, train_image_phase0, train_image_phase1, train_image_phase2
-    import inspect
-    for mod in (evaluate, train_birdview, train_image_phase0, train_image_phase1):
-        assert "resident_entries" in inspect.getsource(mod.main), mod.__name__
-    assert "resident_entries" not in inspect.getsource(train_image_phase2) and "add_resident_arguments" not in inspect.getsource(train_image_phase2)
+    # every script that reads the dataset takes the flag and checks it before it touches the device: with or without a GPU
+    for mod, required in ((evaluate, ["--phase", "1", "--model_path", "unused"]), (train_birdview, ["--log_dir", "unused"]),
+                          (train_image_phase0, ["--log_dir", "unused"]), (train_image_phase1, ["--log_dir", "unused"])):
+        with pytest.raises(SystemExit, match="--dataset_dir"):
+            mod.main(required + ["--resident"])
+    with pytest.raises(SystemExit) as usage:
+        train_image_phase2.main(["--log_dir", "unused", "--resident"])
+    assert usage.value.code == 2, "argparse's usage error: phase 2 does not take the flag"
     base = {"dataset_dir": dataset_dir, "batch_size": 3, "n_step": 5, "gap": 5}
     for extra, cls_name in (({}, "ImageDataset"), ({"crop_x_jitter": 5, "crop_y_jitter": 5, "angle_jitter": 5, "cmd_biased": True}, "BiasedBirdViewDataset")):
         host = make_loaders({"data_args": dict(base, **extra), "iters_per_epoch": 200, "synthetic": 0}, dev)

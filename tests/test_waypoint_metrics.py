@@ -408,7 +408,7 @@ class _TrainerCase:
         self.frame = "map" if phase == "birdview" else "camera"
         self.scale, self.shift = (MAP_SCALE, MAP_SHIFT) if phase == "birdview" else (1.0, 0.0)
 
-    def make(self):
+    def make(self, **keywords):
         from learningbycheating_amd.training.native import NativeTrainer
         student = _models(self.kind, self.dev, self.small, 1)
         student.load_state_dict(self.init["student"])
@@ -417,7 +417,7 @@ class _TrainerCase:
             teacher = _models("birdview", self.dev, self.small, 2)
             teacher.load_state_dict(self.init["teacher"])
         return NativeTrainer(student, teacher, self.n, (7 if self.kind == "birdview" else 3,) + self.hw, self.dev, phase=self.phase, lr=1e-4,
-                             teacher_shape=(7,) + self.thw)
+                             teacher_shape=(7,) + self.thw, **keywords)
 
     def inputs(self, i):
         from oracle import lbc_oracle as O
@@ -641,6 +641,40 @@ def test_script_loops_emulated(env, tmp_path, monkeypatch, module):
     assert rec["train_ade"]["n"] == rec["train_fde"]["n"] == rec["train_bad_rows"]["n"] == 2 and rec["train_ade"]["min"] >= 0
     assert trainer._pass_metrics[True].state()["samples"] == case.n, "the record holds what came after the last logging iteration"
     assert trainer.opt.step_count == 4
+
+
+# the record of one epoch with the options on; every script logs the same keys, phase 1 images_per_sec beside fps
+OPTION_TRAIN_KEYS = {"train_loss_mean", "train_fps", "train_skipped_steps", "train_grad_norm", "train_clip_coef", "train_clipped_steps", "train_lr",
+                     "train_optimizer_steps", "train_dropped_micro_batches", "train_ade", "train_fde", "train_bad_rows"}
+
+
+@pytest.mark.parametrize("module", sorted(PHASE_OF))
+def test_script_loops_log_the_options_keys_emulated(env, tmp_path, module):
+    """the scripts' loop functions with the options on at once -- --accumulate 2, --log-grad-norm, --skip-nonfinite, a constant schedule
+    with a warm-up, --train-metrics: a training pass of four batches and a validation pass log exactly these keys (the epoch record's
+    keys are part of what a log reader depends on; the order inside a record is not)"""
+    import importlib
+    from learningbycheating_amd.bird_view.utils import bz_utils as bzu
+    from learningbycheating_amd.bird_view.utils.datasets.synthetic import SyntheticFrames
+    from learningbycheating_amd.training.data import _SyntheticLoader
+    dev, _ = env
+    script = importlib.import_module("learningbycheating_amd.training." + module)
+    case = _TrainerCase(dev, PHASE_OF[module])
+    schedule = {"kind": "constant", "warmup_steps": 2, "warmup_start": 0.0}
+    trainer = case.make(accumulate=2, max_grad_norm=0.0, skip_nonfinite=True, lr_schedule=schedule)
+    frames = SyntheticFrames(4 * case.n, dev, seed=3, rgb_hw=(32, 64), birdview_hw=(64, 64))
+    config = dict(device=dev, log_iterations=2, rank=0, world_size=1, speed_noise=0.0, accumulate=2, max_grad_norm=0.0, skip_nonfinite=True,
+                  max_skipped=50, lr_schedule=schedule, train_metrics=True)
+    bzu.log.init(str(tmp_path))
+    script.train_or_eval(trainer, _SyntheticLoader(frames, case.n, 4), True, dict(config), False, epoch=1)
+    script.train_or_eval(trainer, _SyntheticLoader(frames, case.n, 2), False, dict(config), False)
+    rec = bzu.log.end_epoch()
+    # (logging iterations 0 and 2: the second window closes after iteration 3, which does not log)
+    assert trainer.opt.step_count == 2 and rec["train_optimizer_steps"]["max"] == 1 and rec["train_dropped_micro_batches"]["max"] == 0
+    want = OPTION_TRAIN_KEYS | {"val_loss_mean", "val_fps"} | ({"train_images_per_sec", "val_images_per_sec"} if module == "train_image_phase1" else set())
+    assert set(rec) - {"epoch", "time"} == want, sorted(set(rec) ^ (want | {"epoch", "time"}))
+    assert rec["train_loss_mean"]["n"] == rec["train_skipped_steps"]["n"] == rec["train_grad_norm"]["n"] == rec["train_ade"]["n"] == 2
+    assert rec["train_fps"]["n"] == 4 and rec["val_fps"]["n"] == rec["val_loss_mean"]["n"] == 2
 
 
 def test_phase1_validation_raises_once_after_the_pass_emulated(env, tmp_path):
