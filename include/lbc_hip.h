@@ -39,7 +39,9 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      lbc_adam_step_recipe (a new descriptor, a new record type that starts with lbc_adam_clip_state's 64 bytes, new exports; the
  *      three existing steps and their records are unchanged).  And the same way: lbc_waypoint_metrics_desc,
  *      lbc_waypoint_metrics_state, lbc_waypoint_metrics_state_bytes, lbc_waypoint_metrics_update (a new descriptor, a new record
- *      type, two new exports; nothing existing changed).
+ *      type, two new exports; nothing existing changed).  And the same way: lbc_agent_desc, lbc_agent_state,
+ *      lbc_agent_state_bytes, lbc_agent_control, lbc_agent_reset (a new descriptor, a new record type, three new exports; nothing
+ *      existing changed).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -420,6 +422,89 @@ typedef struct lbc_waypoint_metrics_state {      /* 248 fields of 8 bytes; [c] c
 size_t lbc_waypoint_metrics_state_bytes(void);
 int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const float* pred, const float* target, const float* command_onehot,
                                 const float* loss /* may be NULL */, int N, void* state, lbc_stream_t stream);
+
+/* The agent half of the tick on the device (csrc/agent.hip): waypoints -> steer / throttle / brake for N independent agents in one
+ * launch, the controller state kept in device memory.  Restates the arithmetic of the reference's two agents and their controllers
+ * (bird_view/models/image.py:124-219 ImageAgent.run_step + unproject, birdview.py:104-174 BirdViewAgent.run_step, controller.py
+ * ls_circle / PIDController / CustomController, common.py:38-51 signed_angle / project_point_to_circle, agent.py postprocess).
+ * Call sequence: hipMemset lbc_agent_state_bytes(N) bytes to zero once (all-zero bytes are N fresh agents), one lbc_agent_control
+ * per tick on the stream of lbc_net_forward_u8 with its pred_sel, lbc_agent_reset at every episode start.  Nothing is read back by
+ * the library; the host copies the N x 8 doubles of `out` when it wants the controls.
+ * One thread per agent, all arithmetic in DOUBLE, no atomics: the same inputs and state give the same bits on every run.
+ * Per active agent i, with (x_k, y_k) = pred[i][k], k < 5, and c = the commanded branch of command_onehot[i] (0..3):
+ *   LBC_AGENT_IMAGE:  a_k = (double)(float)(x_k + 1) * w / 2, b_k = (double)(float)(y_k + 1) * h / 2 (the sum rounded to f32, as the
+ *     reference's f32 array + 1 is), f = w / (2 tan(fov pi / 360)) (computed on the host), xt = (a_k - w / 2) / f, yt = (b_k - h / 2) / f,
+ *     z = world_y / yt, targets[k + 1] = (forward, lateral) = (z - fixed_offset, z xt);
+ *     target_speed = the mean length of the 5 segments of targets[0..5] / (gap dt).
+ *   LBC_AGENT_BIRDVIEW:  (a_k, b_k) = (double)(float)((v + 1) / 2 * crop_size), every step in f32 as the reference's f32 array,
+ *     targets[k + 1] = ((crop_size - b_k) / pixels_per_meter, (a_k - crop_size / 2) / pixels_per_meter);
+ *     target_speed = sum_{k = 1 .. speed_steps - 1} |(a_k, b_k) - (a_{k-1}, b_{k-1})| / (pixels_per_meter gap dt) / (speed_steps - 1).
+ *   Both: targets[0] = (0, 0).  Least-squares circle through the six targets (u, v = coordinates minus their means; Suu, Suv, Svv,
+ *     Suuu, Suvv, Svvv, Svuu their moment sums; the centre solves [[Suu, Suv], [Suv, Svv]] (cx, cy) = ((Suuu + Suvv) / 2, (Svvv + Svuu) / 2)
+ *     by Cramer's rule with det = Suu Svv - Suv^2; r = sqrt(cx^2 + cy^2 + (Suu + Svv) / 6); the means are added back).
+ *     The aim point is targets[steer_points[c]] projected onto the circle, centre + (p - centre) / |p - centre| r, and
+ *     alpha = atan2(aim_y, aim_x), the signed angle of the aim point against the forward axis.
+ *     Steering: alpha enters a window of the last turn_window values; steer = Kp alpha + Kd de + Ki ie with (Kp, Ki, Kd) = turn_pid[c],
+ *     de = (newest - the one before) / dt, ie = (sum of the window, oldest first) dt, both 0 while the window holds fewer than two values.
+ *     Speed: e = target_speed - speed[i] enters a window of the last speed_window values; throttle = Kp e + Ki ie + Kd de the same way
+ *     with speed_pid.  BOTH windows advance on every active tick, braking ticks included.  (The reference's controllers carry
+ *     their own 0.1 s next to the agents' DT = 0.1; here all three are `dt`.)
+ *     IMAGE: target_speed <= engine_brake_threshold -> steer = throttle = 0; target_speed <= brake_threshold -> brake = 1.
+ *     BIRDVIEW: target_speed < stop_threshold -> steer = throttle = 0, brake = 1.
+ *   out[i] = { clip(steer, -1, 1), clip(throttle, 0, 1), clip(brake, 0, 1), target_speed, aim_x, aim_y, alpha, flags }.
+ * Cases the reference leaves undefined (it raises, or divides by zero), decided here; `flags` is a double holding the sum of
+ *   LBC_AGENT_FLAG_DEGENERATE (1): |det| <= 1e-12 Suu Svv (collinear targets -- a car driving dead straight; Suu Svv == 0 included),
+ *     or the steer point lies on the centre: the aim point is targets[steer_points[c]] itself, the limit of the projection as the
+ *     radius grows.  Everything else proceeds normally.
+ *   LBC_AGENT_FLAG_BAD (2): a waypoint that is not finite; IMAGE: a waypoint on or above the horizon row (yt <= 0); a command row
+ *     that is not one-hot (exactly one entry equal to 1, the others 0): out[i] = { 0, 0, 1, 0, 0, 0, 0, 2 } and the windows are NOT touched.
+ *   LBC_AGENT_FLAG_INACTIVE (4): active != NULL and active[i] == 0: the state is not touched, out[i] = { 0, 0, 0, 0, 0, 0, 0, 4 }.
+ * A speed[i] that is not finite is not a bad waypoint: it travels through the speed controller like any other number.
+ * Reads: pred [N][5][2], speed [N], command_onehot [N][4], active [N] (nullable), the N records.  Writes: out [N][8] and the records of
+ * active agents with a good waypoint.  N == 0 launches nothing.
+ * lbc_agent_reset: the records of the agents with mask[i] != 0 (mask == NULL: all N) become all-zero bytes, on `stream`.
+ * Refused with LBC_EINVAL (nothing launched, nothing written): a null or non-8-byte-aligned state or out, null pred / speed /
+ * command_onehot, N < 0, a struct_size other than sizeof(lbc_agent_desc) (start it as `lbc_agent_desc d = LBC_AGENT_DESC_IMAGE_INIT;`
+ * or `... = LBC_AGENT_DESC_BIRDVIEW_INIT;`), an unknown kind, n_steps other than 5, speed_steps outside 2..n_steps, turn_window outside
+ * 2..10, speed_window outside 2..30, a steer point outside 0..n_steps, a gap, dt, fov, w, h, crop_size or pixels_per_meter that is not
+ * a positive finite number (fov < 180), any other field that is not finite. */
+enum { LBC_AGENT_IMAGE = 0, LBC_AGENT_BIRDVIEW = 1 };
+enum { LBC_AGENT_FLAG_DEGENERATE = 1, LBC_AGENT_FLAG_BAD = 2, LBC_AGENT_FLAG_INACTIVE = 4 };
+#define LBC_AGENT_TURN_WINDOW_MAX 10
+#define LBC_AGENT_SPEED_WINDOW_MAX 30
+typedef struct lbc_agent_desc {
+    unsigned struct_size;        /* = sizeof(lbc_agent_desc) */
+    int kind;                    /* LBC_AGENT_* */
+    int n_steps;                 /* waypoints per agent: 5 */
+    int speed_steps;             /* BIRDVIEW: target_speed from the first speed_steps - 1 segments (reference SPEED_STEPS = 3) */
+    double w, h, fov;            /* IMAGE: camera frame in pixels, horizontal field of view in degrees */
+    double world_y, fixed_offset;/* IMAGE: camera height and the forward offset of the unprojection, metres */
+    double crop_size;            /* BIRDVIEW: side of the map crop in pixels */
+    double pixels_per_meter;     /* BIRDVIEW */
+    double gap, dt;              /* waypoints are gap frames of dt seconds apart */
+    int steer_points[4];         /* per command: index into targets[0..n_steps] of the point the car aims at */
+    double turn_pid[4][3];       /* per command: Kp, Ki, Kd of the steering controller */
+    double speed_pid[3];         /* Kp, Ki, Kd of the speed controller */
+    int turn_window, speed_window;   /* 2..10 and 2..30 */
+    double engine_brake_threshold, brake_threshold;   /* IMAGE, m/s */
+    double stop_threshold;       /* BIRDVIEW, m/s */
+} lbc_agent_desc;
+#define LBC_AGENT_DESC_IMAGE_INIT { (unsigned)sizeof(lbc_agent_desc), 0, 5, 3, 384.0, 160.0, 90.0, 1.4, 4.0, 192.0, 5.0, 5.0, 0.1, \
+                                    { 4, 3, 2, 2 }, { { 0.5, 0.2, 0.0 }, { 0.7, 0.1, 0.0 }, { 1.0, 0.1, 0.0 }, { 1.0, 0.5, 0.0 } }, \
+                                    { 0.8, 0.08, 0.0 }, 10, 30, 2.0, 2.0, 1.0 }
+#define LBC_AGENT_DESC_BIRDVIEW_INIT { (unsigned)sizeof(lbc_agent_desc), 1, 5, 3, 384.0, 160.0, 90.0, 1.4, 4.0, 192.0, 5.0, 5.0, 0.1, \
+                                       { 3, 2, 2, 2 }, { { 1.0, 0.1, 0.0 }, { 1.0, 0.1, 0.0 }, { 0.8, 0.1, 0.0 }, { 0.8, 0.1, 0.0 } }, \
+                                       { 1.0, 0.1, 2.5 }, 10, 30, 2.0, 2.0, 1.0 }
+typedef struct lbc_agent_state {     /* one agent's controllers, 336 bytes; all-zero bytes = a fresh agent */
+    double turn_ring[LBC_AGENT_TURN_WINDOW_MAX];      /* the last min(turn_count, turn_window) alphas, slots 0 .. turn_window - 1 in use */
+    double speed_ring[LBC_AGENT_SPEED_WINDOW_MAX];    /* the last speed errors, likewise */
+    int turn_count, turn_head;   /* values held (saturates at the window), slot the next value goes to */
+    int speed_count, speed_head;
+} lbc_agent_state;
+size_t lbc_agent_state_bytes(int n_agents);      /* n_agents * sizeof(lbc_agent_state); 0 for n_agents <= 0 */
+int lbc_agent_control(const lbc_agent_desc* desc, const float* pred, const float* speed, const float* command_onehot,
+                      const unsigned char* active /* may be NULL */, int N, void* state, double* out, lbc_stream_t stream);
+int lbc_agent_reset(const unsigned char* mask /* may be NULL */, int N, void* state, lbc_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-operator entry points of the HBM-bound kernels: what the executor above launches between the

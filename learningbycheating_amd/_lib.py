@@ -109,6 +109,26 @@ class WaypointMetricsState(ctypes.Structure):
                 ("loss_sum", ctypes.c_double), ("loss_bad", ctypes.c_longlong)]
 
 
+class AgentDesc(ctypes.Structure):
+    """lbc_agent_desc (a host struct, read during the call); struct_size is filled in here, everything else by agent.ControllerConfig"""
+    _fields_ = ([("struct_size", ctypes.c_uint), ("kind", c_int), ("n_steps", c_int), ("speed_steps", c_int)] +
+                [(n, ctypes.c_double) for n in ("w", "h", "fov", "world_y", "fixed_offset", "crop_size", "pixels_per_meter", "gap", "dt")] +
+                [("steer_points", c_int * 4), ("turn_pid", ctypes.c_double * 3 * 4), ("speed_pid", ctypes.c_double * 3),
+                 ("turn_window", c_int), ("speed_window", c_int)] +
+                [(n, ctypes.c_double) for n in ("engine_brake_threshold", "brake_threshold", "stop_threshold")])
+
+    def __init__(self, **kw):
+        d = dict(struct_size=ctypes.sizeof(AgentDesc))
+        d.update(kw)
+        super().__init__(**d)
+
+
+class AgentState(ctypes.Structure):
+    """lbc_agent_state: one agent's two PID windows in device memory, 336 bytes; all-zero bytes = a fresh agent"""
+    _fields_ = [("turn_ring", ctypes.c_double * 10), ("speed_ring", ctypes.c_double * 30), ("turn_count", c_int), ("turn_head", c_int),
+                ("speed_count", c_int), ("speed_head", c_int)]
+
+
 _SIGNATURES = {
     "lbc_last_error": (c_char_p, []),
     "lbc_backend": (c_char_p, []),
@@ -157,6 +177,9 @@ _SIGNATURES = {
     "lbc_grad_accumulate": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
     "lbc_waypoint_metrics_state_bytes": (c_size_t, []),
     "lbc_waypoint_metrics_update": (c_int, [ctypes.POINTER(WaypointMetricsDesc)] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
+    "lbc_agent_state_bytes": (c_size_t, [c_int]),
+    "lbc_agent_control": (c_int, [ctypes.POINTER(AgentDesc)] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_void_p]),
+    "lbc_agent_reset": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "lbc_bn_stats": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "lbc_bn_finalize_stats": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 5),
     "lbc_bn_apply_relu_add_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),

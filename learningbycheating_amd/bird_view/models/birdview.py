@@ -3,6 +3,7 @@ on the same gfx950 executor as the student (7-channel 192x192 input, 48x48 soft-
 import torch.nn as nn
 
 from . import common
+from ...agent import Agent, ControllerConfig
 
 STEPS = 5
 SPEED_STEPS = 3
@@ -33,3 +34,16 @@ class BirdViewPolicyModelSS(common.PolicyBase):
         if self.all_branch:
             return location_pred, location_preds
         return location_pred
+
+
+class BirdViewAgent(Agent):
+    """reference birdview.py:82-174 BirdViewAgent: the same constructor arguments and run_step(observations, teaching=False); the
+    observation is the simulator's 320 x 320 x 7 map, cropped on the device (learningbycheating_amd/agent.py DrivingSession)"""
+
+    def __init__(self, steer_points=None, pid=None, gap=5, **kwargs):
+        super().__init__(config=ControllerConfig.birdview(steer_points, pid, gap), **kwargs)
+
+    def run_step(self, observations, teaching=False):
+        """observations: 'birdview' uint8 (320,320,7), 'velocity' (3,), 'command' 1..4 -> control (, the (5,2) normalised waypoints)"""
+        control, waypoints = self._observe(observations, "birdview")
+        return (control, waypoints) if teaching else control

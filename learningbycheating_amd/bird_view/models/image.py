@@ -9,6 +9,7 @@ spatial softmax) -> branch select.
 import torch.nn as nn
 
 from . import common
+from ...agent import Agent, ControllerConfig
 
 CROP_SIZE = 192
 STEPS = 5
@@ -45,3 +46,17 @@ class ImagePolicyModelSS(common.PolicyBase):
         if self.all_branch:
             return location_pred, location_preds
         return location_pred
+
+
+class ImageAgent(Agent):
+    """reference image.py:93-196 ImageAgent: the same constructor arguments and run_step(observations, teaching=False), the tick itself
+    one captured graph that ends in the controls (learningbycheating_amd/agent.py DrivingSession, csrc/agent.hip)"""
+
+    def __init__(self, steer_points=None, pid=None, gap=5, camera_args={'x': 384, 'h': 160, 'fov': 90, 'world_y': 1.4, 'fixed_offset': 4.0},
+                 **kwargs):
+        super().__init__(config=ControllerConfig.image(camera_args, steer_points, pid, gap), **kwargs)
+
+    def run_step(self, observations, teaching=False):
+        """observations: 'rgb' uint8 (160,384,3), 'velocity' (3,), 'command' 1..4 -> control (, the (5,2) normalised waypoints)"""
+        control, waypoints = self._observe(observations, "rgb")
+        return (control, waypoints) if teaching else control

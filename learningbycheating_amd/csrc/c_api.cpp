@@ -67,6 +67,23 @@ int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const flo
     return lbc_waypoint_metrics_launch(desc, pred, target, command_onehot, loss, N, state, (hipStream_t)stream);
 }
 
+size_t lbc_agent_state_bytes(int n_agents) { return n_agents > 0 ? sizeof(lbc_agent_state) * (size_t)n_agents : 0; }
+
+int lbc_agent_control(const lbc_agent_desc* desc, const float* pred, const float* speed, const float* command_onehot,
+                      const unsigned char* active, int N, void* state, double* out, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_agent_desc) == 256 && offsetof(lbc_agent_desc, w) == 16 && offsetof(lbc_agent_desc, gap) == 72 &&
+                  offsetof(lbc_agent_desc, steer_points) == 88 && offsetof(lbc_agent_desc, turn_pid) == 104 &&
+                  offsetof(lbc_agent_desc, speed_pid) == 200 && offsetof(lbc_agent_desc, turn_window) == 224 &&
+                  offsetof(lbc_agent_desc, engine_brake_threshold) == 232, "lbc_agent_desc layout (include/lbc_hip.h)");
+    return lbc_agent_control_launch(desc, pred, speed, command_onehot, active, N, state, out, (hipStream_t)stream);
+}
+
+int lbc_agent_reset(const unsigned char* mask, int N, void* state, lbc_stream_t stream)
+{
+    return lbc_agent_reset_launch(mask, N, state, (hipStream_t)stream);
+}
+
 // Every entry point that takes a descriptor checks it: struct_size must cover the fields of the first checked layout (ABI 200: everything up to
 // and including split_workspace_bytes) and must not exceed this library's struct.  A host built against an OLDER header of the same major
 // ABI (fewer trailing fields) stays valid: whoever appends a field must read it only where struct_size covers it (today the checked

@@ -297,3 +297,9 @@ int lbc_grad_accumulate_launch(const float* g, float* acc, long long n, int firs
 struct lbc_waypoint_metrics_desc;
 int lbc_waypoint_metrics_launch(const lbc_waypoint_metrics_desc* d, const float* pred, const float* target, const float* command_onehot,
                                 const float* loss, int N, void* state, hipStream_t s);
+// agent.hip: waypoints -> steer / throttle / brake for N agents in one launch, one thread per agent, the two PID windows in the device
+// records lbc_agent_state (include/lbc_hip.h); double arithmetic, no atomics.  The descriptor is validated here.
+struct lbc_agent_desc;
+int lbc_agent_control_launch(const lbc_agent_desc* d, const float* pred, const float* speed, const float* command_onehot,
+                             const unsigned char* active, int N, void* state, double* out, hipStream_t s);
+int lbc_agent_reset_launch(const unsigned char* mask, int N, void* state, hipStream_t s);
