@@ -21,80 +21,96 @@ __device__ __forceinline__ unsigned xcd_major_block()
     return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (b >> 3);
 }
 
+// A lane owns one 16-byte channel group of one output column and walks down kPoolRun output rows of one image: the input row
+// under a window is the top row of the next window, so it is loaded and put through the affine once and carried in registers
+// (six 16-byte loads per output vector where nine were, every input row read 1 + 1 / (2 kPoolRun) times), and the addresses
+// advance by a row; the only divisions place the lane.  Lanes are numbered column group fastest, then run, then image, and
+// workgroups take 256 consecutive lanes in XCD-major order.
+constexpr int kPoolRun = 8;
+
 template <typename T, typename IDX>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_k(PoolFwdArgs a)
 {
     constexpr int V = Act<T>::kVec;          // 16-byte accesses: 4 f32 or 8 bf16 channels per thread
     using vec = typename Act<T>::vec;
     using PV = ParamVec<V>;
-    const T* y = static_cast<const T*>(a.y);
-    T* pout = static_cast<T*>(a.p);
     const int OH = a.H / 2, OW = a.W / 2;
     const int cvn = a.C / V;
-    // IDX = unsigned when every index of the launch fits 32 bits (lbc_bn_relu_maxpool_fwd): four 64-bit divisions per element otherwise
-    const IDX total = (IDX)((long long)a.N * OH * OW * cvn);
-    const IDX stride = (IDX)gridDim.x * (IDX)blockDim.x;
-    // (each workgroup owns a contiguous span of ceil(total / grid) elements, spans in XCD-major order: vertical neighbours share an L2)
-    const IDX span = (total + (IDX)gridDim.x - 1) / (IDX)gridDim.x;
-    const IDX i0 = (IDX)xcd_major_block() * span;
-    const IDX i1 = i0 + span < total ? i0 + span : total;
-    (void)stride;
-    for (IDX i = i0 + (IDX)threadIdx.x; i < i1; i += (IDX)blockDim.x) {
-        IDX t = i;
-        const int cg = (int)(t % (IDX)cvn); t /= (IDX)cvn;
-        const int ox = (int)(t % (IDX)OW); t /= (IDX)OW;
-        const int oy = (int)(t % (IDX)OH);
-        const int n = (int)(t / (IDX)OH);
-        const int c = cg * V;
-        const vec sc = PV::ld(a.scale + c), sh = PV::ld(a.shift + c);
-        vec best = PV::splat(-INFINITY);
+    const int lanes_row = OW * cvn, runs = (OH + kPoolRun - 1) / kPoolRun;
+    // IDX = unsigned when the lane count of the launch fits 32 bits (lbc_bn_relu_maxpool_fwd): 64-bit divisions otherwise
+    const IDX u = (IDX)xcd_major_block() * (IDX)256 + (IDX)threadIdx.x;
+    if (u >= (IDX)((long long)a.N * runs * lanes_row)) return;
+    const int sl = (int)(u % (IDX)lanes_row);
+    const IDX t = u / (IDX)lanes_row;
+    const int run = (int)(t % (IDX)runs), n = (int)(t / (IDX)runs);
+    const int ox = sl / cvn, c = (sl - ox * cvn) * V;
+    const int oy0 = run * kPoolRun;
+    const int nrow = OH - oy0 < kPoolRun ? OH - oy0 : kPoolRun;
+    const vec sc = PV::ld(a.scale + c), sh = PV::ld(a.shift + c);
+    const vec ninf = PV::splat(-INFINITY);
+    // of a window's taps only the row above output row 0 and the column left of output column 0 can lie outside (H and W are
+    // even); those are loaded from a clamped, always valid address and enter as -inf, which never beats the running maximum
+    const bool okl = ox > 0, okt = oy0 > 0;
+    const size_t rowe = (size_t)a.W * a.C;
+    const int col[3] = {okl ? -a.C : 0, 0, a.C};
+    const T* src = static_cast<const T*>(a.y) + ((size_t)n * a.H + (size_t)(2 * oy0)) * rowe + (size_t)(2 * ox) * a.C + c;
+    size_t o = (((size_t)n * OH + (size_t)oy0) * OW + (size_t)ox) * a.C + c;
+    T* pout = static_cast<T*>(a.p);
+    vec top[3];
+    {
+        const T* tp = src - (okt ? rowe : 0);
+        typename Act<T>::raw raw[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) raw[s] = Act<T>::ldr(tp + col[s]);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            vec v = Act<T>::cvt(raw[s]);
+            v = v * sc + sh;
+#pragma unroll
+            for (int e = 0; e < V; ++e) top[s][e] = okt && (s > 0 || okl) ? fmaxf(v[e], 0.f) : -INFINITY;
+        }
+    }
+    for (int r = 0; r < nrow; ++r) {
+        typename Act<T>::raw raw[6];         // every load of the two new rows is requested before the first is used
+#pragma unroll
+        for (int q = 0; q < 6; ++q) raw[q] = Act<T>::ldr(src + (q / 3) * rowe + col[q % 3]);
+        vec best = ninf;
         int bi[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) bi[e] = 0;
-        // all nine taps are requested before the first is used (border taps from a clamped, always valid address; they are
-        // dropped below): with `continue` on the border tests every load sat in a block of its own behind an s_waitcnt vmcnt(0)
-        // -- nine memory latencies in a row per output element
-        typename Act<T>::raw raw[9];
-        bool ok[9];
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int iy = 2 * oy - 1 + r;
-            const bool oky = (unsigned)iy < (unsigned)a.H;
-            const int cy = oky ? iy : oy * 2;
+        for (int tap = 0; tap < 9; ++tap) {  // taps in row-major order, strict comparison: the first maximum wins
+            vec z;
+            if (tap < 3) {
+                z = top[tap];
+            } else {
+                vec v = Act<T>::cvt(raw[tap - 3]);
+                v = v * sc + sh;
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const int ix = 2 * ox - 1 + s;
-                const bool okx = (unsigned)ix < (unsigned)a.W;
-                const int cx = okx ? ix : ox * 2;
-                ok[r * 3 + s] = oky && okx;
-                raw[r * 3 + s] = Act<T>::ldr(y + ((size_t)(n * a.H + cy) * a.W + (size_t)cx) * a.C + c);
+                for (int e = 0; e < V; ++e) z[e] = tap % 3 > 0 || okl ? fmaxf(v[e], 0.f) : -INFINITY;
+                if (tap >= 6) top[tap - 6] = z;
             }
-        }
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            vec v = Act<T>::cvt(raw[tap]);
-            v = v * sc + sh;
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const float z = ok[tap] ? fmaxf(v[e], 0.f) : -INFINITY;      // (-inf never beats the running maximum)
-                if (z > best[e]) { best[e] = z; bi[e] = tap; }
-            }
+            for (int e = 0; e < V; ++e)
+                if (z[e] > best[e]) { best[e] = z[e]; bi[e] = tap; }
         }
-        Act<T>::stv(pout + i * V, best);
+        Act<T>::stv(pout + o, best);
         if (a.idx) {
 #pragma unroll
             for (int q = 0; q < V / 4; ++q) {
-                uchar4 u;
-                u.x = (unsigned char)bi[4 * q]; u.y = (unsigned char)bi[4 * q + 1]; u.z = (unsigned char)bi[4 * q + 2]; u.w = (unsigned char)bi[4 * q + 3];
-                reinterpret_cast<uchar4*>(a.idx)[i * (V / 4) + q] = u;
+                uchar4 w;
+                w.x = (unsigned char)bi[4 * q]; w.y = (unsigned char)bi[4 * q + 1]; w.z = (unsigned char)bi[4 * q + 2]; w.w = (unsigned char)bi[4 * q + 3];
+                reinterpret_cast<uchar4*>(a.idx + o)[q] = w;
             }
         }
+        src += 2 * rowe;
+        o += (size_t)OW * a.C;
     }
 }
 
 // Backward: for every stem-output element gather the pooled gradients whose arg-max
 // is this element, apply the ReLU mask, store g and reduce (sum g, sum g*xhat).
-template <typename T, typename IDX>      // IDX = unsigned when the pixel index fits 32 bits (three 64-bit divisions per pixel otherwise)
+template <typename T, typename IDX>      // IDX = unsigned when the pixel index fits 32 bits (64-bit divisions to place the lane's first pixel otherwise)
 __global__ __launch_bounds__(256) void maxpool_relu_bwd_reduce_k(PoolBwdArgs a)
 {
     constexpr int V = Act<T>::kVec;
@@ -118,34 +134,48 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_reduce_k(PoolBwdArgs a)
         const long long p0 = (long long)xcd_major_block() * a.pix_per_block;
         long long p1 = p0 + a.pix_per_block;
         if (p1 > pixels) p1 = pixels;
-        for (long long p = p0 + pl; p < p1; p += rl) {
-            const IDX pi = (IDX)p;
-            const int x = (int)(pi % (IDX)a.W);
+        // (row, column, image) of the lane's pixel: placed once, then advanced by the lane stride
+        int x = 0, yy = 0, n = 0;
+        if (p0 + pl < p1) {
+            const IDX pi = (IDX)(p0 + pl);
+            x = (int)(pi % (IDX)a.W);
             const IDX t = pi / (IDX)a.W;
-            const int yy = (int)(t % (IDX)a.H);
-            const int n = (int)(t / (IDX)a.H);
+            yy = (int)(t % (IDX)a.H);
+            n = (int)(t / (IDX)a.H);
+        }
+        for (long long p = p0 + pl; p < p1; p += rl) {
             vec g = PV::splat(0.f);
             const int oy0 = yy >> 1, oy1 = (yy + 1) >> 1;   // windows covering row y (equal when y is even)
             const int ox0 = x >> 1, ox1 = (x + 1) >> 1;
-            // the (up to) 2 x 2 windows as a fixed set with validity flags, every load requested before the first use (row / column 0
-            // always exist: oy0 <= OH - 1; the second exists when it differs and lies inside) -- the data-dependent loops with
-            // `continue` put each window's two loads behind the previous window's wait
+            // the two windows of the upper pooled row as a fixed pair with a validity flag, the two of the lower one under `rok`: a
+            // pooled row serves the two or three rows under it, and an even row (or the last one) lies under one pooled row only.
+            // The lanes of a wave mostly share a row, so the wave skips those loads and comparisons.  Every load is requested
+            // before the first use (column 0 always exists; the second exists when it differs and lies inside).
             const bool rok = oy1 != oy0 && oy1 < OH, cok = ox1 != ox0 && ox1 < OW;
-            const int oyw[2] = {oy0, rok ? oy1 : oy0}, oxw[2] = {ox0, cok ? ox1 : ox0};
+            const int oxw[2] = {ox0, cok ? ox1 : ox0};
+            const int tx[2] = {x - (2 * ox0 - 1), x - (2 * ox1 - 1)};
             typename Act<T>::raw draw[4];
             uchar4 uraw[4][V / 4];
+            const size_t orow = (size_t)(n * OH + oy0) * OW;
 #pragma unroll
-            for (int wv = 0; wv < 4; ++wv) {
-                const size_t o = ((size_t)(n * OH + oyw[wv >> 1]) * OW + (size_t)oxw[wv & 1]) * cvn + cg;
+            for (int wv = 0; wv < 2; ++wv) {
+                const size_t o = (orow + (size_t)oxw[wv]) * cvn + cg;
                 draw[wv] = Act<T>::ldr(dp + o * V);
 #pragma unroll
                 for (int q = 0; q < V / 4; ++q) uraw[wv][q] = reinterpret_cast<const uchar4*>(a.idx)[o * (V / 4) + q];
             }
-            const typename Act<T>::raw yraw = Act<T>::ldr(y + (p * cvn + cg) * V);
+            if (rok) {
 #pragma unroll
-            for (int wv = 0; wv < 4; ++wv) {                // same order as the loops it replaces: (oy0, ox0), (oy0, ox1), (oy1, ox0), (oy1, ox1)
-                const bool okw = ((wv >> 1) == 0 || rok) && ((wv & 1) == 0 || cok);
-                const int tap = okw ? (yy - (2 * oyw[wv >> 1] - 1)) * 3 + (x - (2 * oxw[wv & 1] - 1)) : 255;     // 255: no arg-max index matches
+                for (int wv = 2; wv < 4; ++wv) {
+                    const size_t o = (orow + (size_t)OW + (size_t)oxw[wv & 1]) * cvn + cg;
+                    draw[wv] = Act<T>::ldr(dp + o * V);
+#pragma unroll
+                    for (int q = 0; q < V / 4; ++q) uraw[wv][q] = reinterpret_cast<const uchar4*>(a.idx)[o * (V / 4) + q];
+                }
+            }
+            const typename Act<T>::raw yraw = Act<T>::ldr(y + (p * cvn + cg) * V);
+            // in the order (oy0, ox0), (oy0, ox1), (oy1, ox0), (oy1, ox1)
+            auto gather = [&](int wv, int tap) {
                 const vec d = Act<T>::cvt(draw[wv]);
 #pragma unroll
                 for (int q = 0; q < V / 4; ++q) {
@@ -155,6 +185,13 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_reduce_k(PoolBwdArgs a)
                     if (u.z == tap) g[4 * q + 2] += d[4 * q + 2];
                     if (u.w == tap) g[4 * q + 3] += d[4 * q + 3];
                 }
+            };
+            const int ty = (yy - (2 * oy0 - 1)) * 3;
+            gather(0, ty + tx[0]);
+            gather(1, cok ? ty + tx[1] : 255);              // (255: no arg-max index matches)
+            if (rok) {                                      // (yy - (2 oy1 - 1) = 0: the top row of the lower windows)
+                gather(2, tx[0]);
+                gather(3, cok ? tx[1] : 255);
             }
             const vec v = Act<T>::cvt(yraw);
             const vec z = v * sc + sh;
@@ -163,6 +200,11 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_reduce_k(PoolBwdArgs a)
             Act<T>::stv(gout + (p * cvn + cg) * V, g);
             s1 += g;
             s2 += g * (v - mean) * inv;
+            x += rl;
+            while (x >= a.W) {
+                x -= a.W;
+                if (++yy == a.H) { yy = 0; ++n; }
+            }
         }
     }
     PV::st(red + threadIdx.x * V, s1);
@@ -186,10 +228,12 @@ int lbc_bn_relu_maxpool_fwd(const PoolFwdArgs& a, hipStream_t s)
 {
     LBC_REQUIRE(a.C % 8 == 0 && a.H % 2 == 0 && a.W % 2 == 0, "maxpool: bad shape");
     const long long total = (long long)a.N * (a.H / 2) * (a.W / 2) * (a.C / 4);
-    long long blocks = (total / (a.act_bf16 ? 2 : 1) + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const int OH = a.H / 2;
+    const long long lanes = (long long)a.N * ((OH + kPoolRun - 1) / kPoolRun) * (a.W / 2) * (a.C / (a.act_bf16 ? 8 : 4));
+    const long long blocks = (lanes + 255) / 256;
+    LBC_REQUIRE(blocks < (1ll << 31), "maxpool: too large");
     LbcProfScope prof("bn_relu_maxpool_fwd", 0.0, (a.act_bf16 ? 2.0 : 4.0) * total * 4 * (4.0 + 1.0) + total * 4.0, s);
-    const bool small = total + blocks * 256 < (1ll << 31);       // (the loop index passes `total` by less than one grid stride)
+    const bool small = lanes + 256 < (1ll << 32);
 #define LBC_K(T, g)                                                                                                          \
     do {                                                                                                                     \
         if (small) hipLaunchKernelGGL((bn_relu_maxpool_fwd_k<T, unsigned>), dim3((unsigned)(g)), dim3(256), 0, s, a);        \

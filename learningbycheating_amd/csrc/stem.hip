@@ -13,6 +13,7 @@
 #include "lbc_common.hpp"
 #include "lbc_act.hpp"
 #include "lbc_kernels.hpp"
+#include <cstdint>
 #include <type_traits>
 
 namespace {
@@ -48,38 +49,115 @@ __global__ __launch_bounds__(256) void prep_input_k(const float* __restrict__ im
 
 // uint8 NHWC frames (what the LMDB dataset stores: reference bird_view/utils/datasets/image_lmdb.py:128-222 decodes them to
 // f32 CHW on the host): /255, ImageNet normalisation and the zero border in one pass, 4x fewer input bytes
-// CIN = 3 / 7 (the two networks) unrolls the channel loop with every byte load in front of the first use (with the channel count
-// a runtime value each 1-byte load was followed by its own s_waitcnt vmcnt(0)); CIN = 0: any C <= 8.  IDX = unsigned when the
-// padded pixel index fits 32 bits.
-template <typename XT, int CIN, typename IDX>
+//
+// The padded image is written as a stream of 16-byte pieces (V = 8 bf16 or 4 f32 elements per lane), counted from the 16-byte
+// boundary at or below xp: the first and the last piece may be partial and are then stored element by element.  A row of the
+// padded image is RL = (W + 6) * C elements; a lane keeps (image, padded row, offset in the row) of its piece and advances them
+// by the launch's stride (PrepSweep, split into rows and elements on the host), so the only divisions are the two that place its
+// first piece.  The value of a byte depends on (byte, channel) alone: each workgroup tabulates the 256 * C results in LDS with the
+// very expressions of the per-pixel code, so every element costs one table read and no division, and the result is bit-identical.
+//
+// WORDS (C = 3 / 7, frames on a 4-byte boundary and a whole number of words): the V source bytes of a piece are contiguous in
+// the frame row and are cut out of V / 4 + 1 aligned 4-byte loads.  3 * C >= V - 1 there, so whatever a piece holds of the next
+// padded row is border.  Otherwise (CIN = 0: any C <= 8, any pointer) the bytes are loaded one by one, all before the first use.
+// IDX = unsigned when the element count of the padded image fits 31 bits.
+struct PrepSweep { int dn, dy, dj; };     // one grid stride of pieces = dn images + dy padded rows + dj elements
+
+template <typename XT, int CIN, bool WORDS, typename IDX>
 __global__ __launch_bounds__(256) void prep_input_u8_k(const unsigned char* __restrict__ img, XT* __restrict__ xp, int N, int C,
-                                                       int H, int W, NormConst nc)
+                                                       int H, int W, NormConst nc, PrepSweep sw)
 {
-    const int Hp = H + 6, Wp = W + 6;
+    constexpr int V = 16 / (int)sizeof(XT);
+    typedef XT xvec __attribute__((ext_vector_type(V)));
+    static_assert(!WORDS || 3 * CIN >= V - 1, "prep_input: a piece must not reach the next row's frame");
+    __shared__ XT tab[8 * 256];
     const int Cc = CIN ? CIN : C;
-    const IDX total = (IDX)((long long)N * Hp * Wp);
-    const IDX stride = (IDX)gridDim.x * (IDX)blockDim.x;
-    for (IDX i = (IDX)blockIdx.x * (IDX)blockDim.x + (IDX)threadIdx.x; i < total; i += stride) {
-        const int xq = (int)(i % (IDX)Wp);
-        const IDX t = i / (IDX)Wp;
-        const int yq = (int)(t % (IDX)Hp);
-        const int n = (int)(t / (IDX)Hp);
-        const int x = xq - 3, y = yq - 3;
-        const bool in = (unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H;
-        XT* dst = xp + (size_t)i * Cc;
-        const unsigned char* src = img + ((size_t)(n * H + (in ? y : 0)) * W + (size_t)(in ? x : 0)) * Cc;
-        unsigned char b[CIN ? CIN : 8];
-#pragma unroll
-        for (int c = 0; c < (CIN ? CIN : 8); ++c) b[c] = c < Cc ? src[c] : (unsigned char)0;
+    {
+        const unsigned char b = (unsigned char)threadIdx.x;
+        const float u = (float)b / 255.0f;                         // torchvision ToTensor
 #pragma unroll
         for (int c = 0; c < (CIN ? CIN : 8); ++c) {
             if (c >= Cc) break;
-            // selects instead of branches: the loads above stay in front, border lanes (clamped address) discard what they read
-            const float u = (float)b[c] / 255.0f;                  // torchvision ToTensor
             const float w = (u - nc.mean[c]) / nc.stdv[c];         // (discarded, possibly inf / nan, when normalisation is off)
-            const float v = nc.enabled ? w : u;
-            dst[c] = (XT)(in ? v : 0.f);
+            tab[c * 256 + threadIdx.x] = (XT)(nc.enabled ? w : u);
         }
+    }
+    __syncthreads();
+    const int Hp = H + 6, RL = (W + 6) * Cc, WC = W * Cc;
+    const long long total = (long long)N * Hp * RL;
+    const int mis = (int)((reinterpret_cast<uintptr_t>(xp) / sizeof(XT)) % V);      // elements between the 16-byte boundary and xp
+    const IDX npieces = (IDX)((total + mis + V - 1) / V);
+    const IDX stride = (IDX)gridDim.x * (IDX)256;
+    IDX k = (IDX)blockIdx.x * (IDX)256 + (IDX)threadIdx.x;
+    int n = 0, yq = 0, j = -mis;            // piece 0 of a misaligned xp starts `mis` elements in front of row 0
+    if (k > 0) {
+        const IDX f = k * (IDX)V - (IDX)mis;
+        const IDX row = f / (IDX)RL;
+        j = (int)(f - row * (IDX)RL);
+        n = (int)(row / (IDX)Hp);
+        yq = (int)(row - (IDX)n * (IDX)Hp);
+    }
+    const long long nwords = (long long)N * H * WC / 4;
+    for (; k < npieces; k += stride) {
+        const long long f0 = (long long)k * V - mis;
+        int c = (j + 8 * Cc) % Cc;                                 // (j >= -7) channel of element 0; RL is a multiple of C
+        unsigned char b[V];
+        bool ok[V];
+        if (WORDS) {
+            const bool rowin = (unsigned)(yq - 3) < (unsigned)H;
+            const int o = j - 3 * Cc;                              // element 0's offset in the frame row
+            const long long s0 = (rowin ? (long long)(n * H + (yq - 3)) * WC : 0) + o;
+            const long long w0 = s0 >> 2;
+            const int sh = 8 * (int)(s0 & 3);
+            unsigned wd[V / 4 + 1];
+#pragma unroll
+            for (int q = 0; q < V / 4 + 1; ++q) {                  // (clamped words hold no byte of a valid element)
+                long long wi = w0 + q;
+                wi = wi < 0 ? 0 : (wi < nwords ? wi : nwords - 1);
+                wd[q] = reinterpret_cast<const unsigned*>(img)[wi];
+            }
+#pragma unroll
+            for (int q = 0; q < V / 4; ++q) {
+                const unsigned d = (unsigned)(((((unsigned long long)wd[q + 1]) << 32) | wd[q]) >> sh);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    b[4 * q + e] = (unsigned char)(d >> (8 * e));
+                    ok[4 * q + e] = rowin && (unsigned)(o + 4 * q + e) < (unsigned)WC;
+                }
+            }
+        } else {
+            // the piece may run into the next padded row, whose frame bytes lie elsewhere
+            const int yq1 = yq + 1 == Hp ? 0 : yq + 1, n1 = yq + 1 == Hp ? n + 1 : n;
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const bool nxt = j + e >= RL;
+                const int o = (nxt ? j + e - RL : j + e) - 3 * Cc, y = (nxt ? yq1 : yq) - 3, nn = nxt ? n1 : n;
+                ok[e] = (unsigned)y < (unsigned)H && (unsigned)o < (unsigned)WC && nn < N;
+                b[e] = img[ok[e] ? (size_t)(nn * H + y) * WC + (size_t)o : (size_t)0];
+            }
+        }
+        xvec out;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            out[e] = ok[e] ? tab[c * 256 + b[e]] : (XT)0.f;
+            c = c + 1 == Cc ? 0 : c + 1;
+        }
+        if (f0 >= 0 && f0 + V <= total) {
+            *reinterpret_cast<xvec*>(xp + f0) = out;
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e)
+                if (f0 + e >= 0 && f0 + e < total) xp[f0 + e] = out[e];
+        }
+        // (piece 0 of a misaligned xp started at j = -mis: where dj < mis its next piece starts in the END of the row before
+        // the one the stride leads to, so a negative j borrows a row; a stride is at least 1024 elements, hence a row or dj >= 8)
+        j += sw.dj;
+        const int carry = j >= RL ? 1 : (j < 0 ? -1 : 0);
+        j -= carry * RL;
+        yq += sw.dy + carry;
+        n += sw.dn;
+        if (yq >= Hp) { yq -= Hp; ++n; }
+        if (yq < 0) { yq += Hp; --n; }
     }
 }
 
@@ -809,20 +887,28 @@ int lbc_prep_input_u8(const unsigned char* img_nhwc, void* xp, int xp_bf16, int 
 {
     LBC_REQUIRE(C <= 8, "prep_input: at most 8 channels");
     const long long total = (long long)N * (H + 6) * (W + 6);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    if (total * C <= 0) return LBC_OK;                        // nothing to write
+    // no frame byte to read (the clamped loads of the kernel here need one): all border, which the f32 kernel writes without a load
+    if ((long long)N * H * W == 0) return lbc_prep_input(nullptr, xp, xp_bf16, N, C, H, W, nc, s);
     LbcProfScope prof("prep_input", 0.0, 1.0 * N * H * (double)W * C + (xp_bf16 ? 2.0 : 4.0) * (double)total * C, s);
-    const bool small = total + blocks * 256 < (1ll << 31);
-#define LBC_PU(XT, CINv)                                                                                                                 \
+    const int V = xp_bf16 ? 8 : 4;                            // elements per 16-byte piece (see the kernel)
+    long long blocks = (total * C / V + 1 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const long long RL = (long long)(W + 6) * C, rows = blocks * 256 * V / RL;
+    const PrepSweep sw = {(int)(rows / (H + 6)), (int)(rows % (H + 6)), (int)(blocks * 256 * V % RL)};
+    const bool small = total * C + 16 < (1ll << 31);
+    // aligned 4-byte loads need the frames on a 4-byte boundary and no partial last word
+    const bool words = (C == 3 || C == 7) && reinterpret_cast<uintptr_t>(img_nhwc) % 4 == 0 && (long long)N * H * W * C % 4 == 0;
+#define LBC_PU(XT, CINv, WORDSv)                                                                                                         \
     do {                                                                                                                                 \
-        if (small) hipLaunchKernelGGL((prep_input_u8_k<XT, CINv, unsigned>), dim3((unsigned)blocks), dim3(256), 0, s, img_nhwc, static_cast<XT*>(xp), N, C, H, W, nc);  \
-        else       hipLaunchKernelGGL((prep_input_u8_k<XT, CINv, long long>), dim3((unsigned)blocks), dim3(256), 0, s, img_nhwc, static_cast<XT*>(xp), N, C, H, W, nc); \
+        if (small) hipLaunchKernelGGL((prep_input_u8_k<XT, CINv, WORDSv, unsigned>), dim3((unsigned)blocks), dim3(256), 0, s, img_nhwc, static_cast<XT*>(xp), N, C, H, W, nc, sw);  \
+        else       hipLaunchKernelGGL((prep_input_u8_k<XT, CINv, WORDSv, long long>), dim3((unsigned)blocks), dim3(256), 0, s, img_nhwc, static_cast<XT*>(xp), N, C, H, W, nc, sw); \
     } while (0)
 #define LBC_PUC(XT)                                                                                                                      \
     do {                                                                                                                                 \
-        if (C == 3) LBC_PU(XT, 3);                                                                                                       \
-        else if (C == 7) LBC_PU(XT, 7);                                                                                                  \
-        else LBC_PU(XT, 0);                                                                                                              \
+        if (words && C == 3) LBC_PU(XT, 3, true);                                                                                        \
+        else if (words) LBC_PU(XT, 7, true);                                                                                             \
+        else LBC_PU(XT, 0, false);                                                                                                       \
     } while (0)
     if (xp_bf16) LBC_PUC(__bf16);
     else         LBC_PUC(float);
