@@ -641,6 +641,31 @@ int lbc_replay_scatter_u8(const unsigned char* src, long long row_bytes, const i
 int lbc_replay_meta(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, lbc_stream_t stream);
 int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, lbc_stream_t stream);
 
+/* A replay buffer over a resident dataset holds frame INDICES instead of frames (training/replay.py DeviceReplayBuffer(source=...)).
+ * lbc_replay_gather_indirect_u8: dst row b * reps + k = src row frame_of_slot[idx[b]], k < reps: lbc_replay_gather_u8 with a second
+ *   index level, the same argument rules.  Both index levels are trusted.
+ * lbc_replay_admit: m scored candidates (cw, cframe, ccmd, cspeed, each [m]) into a buffer of n occupied slots out of `limit`, in one
+ *   launch of one workgroup; what m ReplayBuffer.add_data calls of the reference decide (phase2_utils.py:256-265), ties made definite.
+ *   The slot arrays weights f32 / frame i32 / cmd i32 / speed f32, each [limit], and slot_of_frame i32 [F] (the slot that holds a frame,
+ *   -1 = not stored) are read and written in place.  cframe must be distinct and inside [0, F): the caller checks, the kernel trusts.
+ *   With key(w) = w if w is finite and >= 0, else -1 (unusable weights rank lowest; stored VALUES stay raw, as lbc_replay_cdf expects):
+ *     1. refresh  a candidate whose frame is stored (slot_of_frame[f] >= 0) overwrites that slot's weight and takes no further part;
+ *     2. append   the remaining candidates fill slots n, n + 1, ... in candidate order while there is room;
+ *     3. compete  once the buffer is full, stored slots and the candidates still waiting are ranked by key descending, stored before
+ *                 waiting at equal key, lower slot / candidate index first; the first `limit` stay; the evicted slots in ascending order
+ *                 receive the surviving candidates in candidate order (frame, cmd, speed, raw weight).  A candidate appended in step 2
+ *                 can be evicted by a later one of the same call.
+ *   slot_of_frame is -1 for every evicted frame and the new slot for every admitted one.  record (device memory, 4 ints) =
+ *   {n_after, refreshed, admitted, evicted}: occupied slots at the end; the count of step 1; candidates that occupy a slot at the end;
+ *   frames stored before the call and gone after it.  No atomics: the result is a function of the inputs.  1 <= limit <= 2^20,
+ *   1 <= m <= 2^20, 0 <= n <= limit, workspace_bytes >= lbc_replay_admit_workspace(limit, m) (device memory, contents irrelevant; the
+ *   query returns 0 outside those ranges); anything else is LBC_EINVAL and launches nothing. */
+int lbc_replay_gather_indirect_u8(const unsigned char* src, long long row_bytes, const int* frame_of_slot, const int* idx, int B, int reps,
+                                  unsigned char* dst, lbc_stream_t stream);
+size_t lbc_replay_admit_workspace(int limit, int m);
+int lbc_replay_admit(float* weights, int* frame, int* cmd, float* speed, int* slot_of_frame, int F, int n, int limit, const float* cw, const int* cframe,
+                     const int* ccmd, const float* cspeed, int m, void* workspace, size_t workspace_bytes, int* record, lbc_stream_t stream);
+
 /* Device-resident LMDB dataset (bird_view/utils/datasets/resident.py): the per-sample work of the host loader -- frame look-up, crop or
  * rotation of the bird-view map, waypoints -- over a batch of frames that live in HBM.  The host draws and uploads one record of four
  * int32 per sample, `draws[b] = (frame index, delta_angle in degrees, dx, dy)`; every call only enqueues on `stream`.  Indices are

@@ -201,6 +201,9 @@ _SIGNATURES = {
     "lbc_replay_cdf": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "lbc_replay_sample": (c_int, [c_void_p, c_int, ctypes.c_uint, ctypes.c_ulonglong, c_int, c_void_p, c_void_p]),
     "lbc_replay_gather_u8": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "lbc_replay_gather_indirect_u8": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "lbc_replay_admit_workspace": (c_size_t, [c_int, c_int]),
+    "lbc_replay_admit": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 4 + [c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "lbc_replay_scatter_u8": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "lbc_replay_meta": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lbc_replay_writeback": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -285,6 +285,24 @@ int lbc_replay_gather_u8(const unsigned char* src, long long row_bytes, const in
     return lbc_replay_gather_launch(src, row_bytes, idx, B, reps, dst, (hipStream_t)stream);
 }
 
+int lbc_replay_gather_indirect_u8(const unsigned char* src, long long row_bytes, const int* frame_of_slot, const int* idx, int B, int reps,
+                                  unsigned char* dst, lbc_stream_t stream)
+{
+    return lbc_replay_gather_indirect_launch(src, row_bytes, frame_of_slot, idx, B, reps, dst, (hipStream_t)stream);
+}
+
+size_t lbc_replay_admit_workspace(int limit, int m)
+{
+    return lbc_replay_admit_workspace_bytes(limit, m);
+}
+
+int lbc_replay_admit(float* weights, int* frame, int* cmd, float* speed, int* slot_of_frame, int F, int n, int limit, const float* cw, const int* cframe,
+                     const int* ccmd, const float* cspeed, int m, void* workspace, size_t workspace_bytes, int* record, lbc_stream_t stream)
+{
+    return lbc_replay_admit_launch(weights, frame, cmd, speed, slot_of_frame, F, n, limit, cw, cframe, ccmd, cspeed, m, workspace, workspace_bytes, record,
+                                   (hipStream_t)stream);
+}
+
 int lbc_replay_scatter_u8(const unsigned char* src, long long row_bytes, const int* slot, int M, unsigned char* dst, lbc_stream_t stream)
 {
     return lbc_replay_scatter_launch(src, row_bytes, slot, M, dst, (hipStream_t)stream);

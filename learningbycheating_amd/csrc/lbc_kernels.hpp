@@ -241,6 +241,12 @@ int lbc_augment_u8(unsigned char* img, const AugParams* params_dev, float* tmp, 
 int lbc_replay_cdf_launch(const float* w, int n, double* cdf, long long* bad_count, hipStream_t s);
 int lbc_replay_sample_launch(const double* cdf, int n, unsigned seed, unsigned long long step, int B, int* idx, hipStream_t s);
 int lbc_replay_gather_launch(const unsigned char* src, long long row_bytes, const int* idx, int B, int reps, unsigned char* dst, hipStream_t s);
+int lbc_replay_gather_indirect_launch(const unsigned char* src, long long row_bytes, const int* frame_of_slot, const int* idx, int B, int reps,
+                                      unsigned char* dst, hipStream_t s);
+size_t lbc_replay_admit_workspace_bytes(int limit, int m);
+int lbc_replay_admit_launch(float* weights, int* frame, int* cmd, float* speed, int* slot_of_frame, int F, int n, int limit, const float* cw,
+                            const int* cframe, const int* ccmd, const float* cspeed, int m, void* workspace, size_t workspace_bytes, int* record,
+                            hipStream_t s);
 int lbc_replay_scatter_launch(const unsigned char* src, long long row_bytes, const int* slot, int M, unsigned char* dst, hipStream_t s);
 int lbc_replay_meta_launch(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, hipStream_t s);
 int lbc_replay_writeback_launch(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, hipStream_t s);

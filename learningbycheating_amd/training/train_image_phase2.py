@@ -11,7 +11,13 @@ the optimizer is re-created every epoch exactly as the reference does (train_ima
 fused u8 input pass and the weight write-back are kernels, and the loop body has no host round trip outside logging iterations.  With it
 come the reference buffer's --augment / --aug_fix_iter / --batch_aug (phase2_utils.py:191,224-234) and --save_state / --resume / --seed:
 log_dir/train_state.th after every epoch (student, buffer state, augmenter stream, RNG, (episode, epoch)); a resumed run continues with
-the next epoch bit for bit."""
+the next epoch bit for bit.
+
+--dataset_dir DIR (with --replay device) trains on a recorded dataset: the train split is read once and kept in HBM (ResidentLoader),
+and every episode begins with an offline rollout (training/rollout.py): --rollout_frames recorded frames are scored with the current
+student against the teacher, both in eval mode, and admitted into a buffer of --buffer_limit slots that holds frame indices into the
+resident dataset (lbc_replay_admit keeps the highest weights).  Then the epochs above run on it.  The states are the recorded ones, not
+the student's own: this is loss-prioritised replay over the dataset, the learner half of DAgger without its on-policy data."""
 import argparse
 import ctypes
 import time
@@ -138,6 +144,24 @@ def synthetic_buffer_device(n_frames, device, seed=0):
     return buf
 
 
+def dataset_buffer(config, trainer, seed=None):
+    """--dataset_dir: the train split resident in HBM the way train_image_phase1 --resident holds it (no teacher cache: phase 2 runs
+    the teacher), an empty buffer of this rank's share of --buffer_limit slots that indexes it, and the rollout that fills it from this
+    rank's share of the frames, --rollout_frames / world of them per episode.  -> (buffer, rollout)"""
+    from ..bird_view.utils.datasets.image_lmdb import ImageDataset
+    from ..bird_view.utils.datasets.resident import ResidentLoader
+    from .rollout import OfflineRollout
+    rank, world, device = config["rank"], config["world_size"], config["device"]
+    data = ImageDataset(str(Path(config["dataset_dir"]) / "train"))
+    store = ResidentLoader(data, config["batch_size"], 0, device, seed=0, rank=rank, reserve_gb=config.get("resident_reserve_gb"))
+    buf = DeviceReplayBuffer(device, buffer_limit=max(1, config["buffer_limit"] // world), seed=rank, source=store)
+    per_rank = config["rollout_frames"] // world if config["rollout_frames"] else 0
+    if config["rollout_frames"] and per_rank < 1:
+        raise SystemExit("train_image_phase2: --rollout_frames %d is less than one frame per rank" % config["rollout_frames"])
+    rollout = OfflineRollout(store, trainer, buf, per_rank, seed=0 if seed is None else int(seed), rank=rank, world=world)
+    return buf, rollout
+
+
 def make_augmenter(config):
     """the reference buffer's augmenter (phase2_utils.py:201-204,225-226): the recipe at the FIXED image counter aug_fix_iter"""
     strategy = augmenter_mod.get(config.get("augment"))
@@ -165,9 +189,10 @@ def _state_path(config):
     return resume._path(config["log_dir"], config["rank"])
 
 
-def save_state_device(config, net, replay_buffer, augmenter, episode, epoch):
+def save_state_device(config, net, replay_buffer, augmenter, episode, epoch, rollout=None):
     """train_state.th (rank 0; train_state.rank%d.th on the others) after epoch `epoch` of episode `episode`.  The optimizer is
-    re-created at every epoch, so there are no moments to keep; synthetic frames are a function of the seed and are not written."""
+    re-created at every epoch, so there are no moments to keep; synthetic frames are a function of the seed and are not written.
+    With --dataset_dir the buffer's part is frame indices, and the rollout's permutation and generator are kept beside it."""
     if not config.get("save_state"):
         return
     device = config["device"]
@@ -175,6 +200,8 @@ def save_state_device(config, net, replay_buffer, augmenter, episode, epoch):
             "rank": int(config["rank"]), "buffer": replay_buffer.state_dict(include_frames=not config.get("synthetic_frames", True)),
             "aug": augmenter.state_dict() if augmenter is not None else None,
             "rng": {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device)}}
+    if rollout is not None:
+        part["rollout"] = rollout.state_dict()
     if config["rank"] == 0:
         part["student"] = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     resume._atomic_save(part, _state_path(config))
@@ -182,7 +209,7 @@ def save_state_device(config, net, replay_buffer, augmenter, episode, epoch):
         dist.barrier()
 
 
-def load_state_device(config, trainer, replay_buffer, augmenter):
+def load_state_device(config, trainer, replay_buffer, augmenter, rollout=None):
     """-> (episode, epoch) to continue with, (0, 0) when log_dir has no state.  The student comes from rank 0's file on every rank,
     buffer / augmenter / RNG from the rank's own."""
     first = resume._path(config["log_dir"], 0)
@@ -210,7 +237,11 @@ def load_state_device(config, trainer, replay_buffer, augmenter):
     if mine is not None:
         if (mine["aug"] is None) != (augmenter is None):
             raise ValueError("the state was saved %s augmentation, this run has %s" % (("without", "with") if mine["aug"] is None else ("with", "without")))
+        if (mine.get("rollout") is None) != (rollout is None):
+            raise ValueError("the state was saved %s --dataset_dir, this run is %s it" % (("without", "with") if rollout is not None else ("with", "without")))
         replay_buffer.load_state_dict(mine["buffer"])
+        if rollout is not None:
+            rollout.load_state_dict(mine["rollout"])
         if augmenter is not None:
             augmenter.load_state_dict(mine["aug"])
         torch.set_rng_state(mine["rng"]["cpu"])
@@ -223,7 +254,18 @@ def load_state_device(config, trainer, replay_buffer, augmenter):
     return episode, epoch
 
 
-def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start_epoch=0, on_epoch_end=None):
+def _epoch_steps(replay_buffer, config):
+    """whole batches in the buffer.  With --dataset_dir under several ranks the buffers fill at their own pace (a rank's rollout refreshes
+    what ITS buffer holds), and every step is a collective: all ranks take the smallest count."""
+    steps = len(replay_buffer) // config["batch_size"]
+    if config.get("dataset_dir") and config.get("world_size", 1) > 1:
+        least = torch.tensor([steps], dtype=torch.int64, device=config["device"])
+        dist.all_reduce(least, op=dist.ReduceOp.MIN)
+        steps = int(least)
+    return steps
+
+
+def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start_epoch=0, on_epoch_end=None, rollout=None):
     """_train on a DeviceReplayBuffer: the same epoch, with no .cpu() / .item() / .numpy() in the loop body outside logging iterations"""
     bs = config["batch_size"]
     net = trainer.student
@@ -232,7 +274,7 @@ def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start
         net.train()
         replay_buffer.init_new_weights()
         windows = resume.Windows(config, trainer)
-        for i in range(len(replay_buffer) // bs):                                              # drop_last=True
+        for i in range(_epoch_steps(replay_buffer, config)):                                   # drop_last=True
             _, loss = _device_step(replay_buffer, trainer, config, augmenter)
             windows.after_step(True)
             if i % int(config["log_iterations"]) == 0:
@@ -246,7 +288,7 @@ def _train_device(replay_buffer, trainer, config, episode, augmenter=None, start
         trainer.eng.forward(rgb, speed, command, False)
         net.train()
         bzu.log.end_epoch()
-        save_state_device(config, net, replay_buffer, augmenter, episode, epoch)
+        save_state_device(config, net, replay_buffer, augmenter, episode, epoch, rollout)
         if on_epoch_end is not None:
             on_epoch_end(episode, epoch, replay_buffer, trainer)
     if episode in SAVE_EPISODES and config["rank"] == 0:
@@ -264,7 +306,15 @@ def parse_arguments(argv=None):
     parser.add_argument("--batch_size", type=int, default=128)
     parser.add_argument("--speed_noise", type=float, default=0.0)
     parser.add_argument("--lr", type=float, default=1e-4)
-    parser.add_argument("--synthetic", type=int, default=20000, help="frames in the synthetic replay buffer")
+    parser.add_argument("--synthetic", type=int, default=None, help="frames in the synthetic replay buffer (default 20000)")
+    parser.add_argument("--dataset_dir", default=None,
+                        help="with --replay device: train on the recorded frames of DIR/train, resident in HBM; every episode scores --rollout_frames of "
+                             "them with the current student and admits them into the replay buffer (recorded states, not the student's own)")
+    parser.add_argument("--rollout_frames", type=int, default=4000,
+                        help="with --dataset_dir: frames scored per episode, over all ranks (0 = the whole dataset; the reference: 4 weathers x 1000)")
+    parser.add_argument("--buffer_limit", type=int, default=100000, help="with --dataset_dir: slots of the replay buffer, over all ranks")
+    parser.add_argument("--resident-reserve-gb", type=float, default=None, metavar="GB",
+                        help="with --dataset_dir: device memory to leave free for networks and workspaces (default: what batch 256 in fp32 needs)")
     loop.add_precision_argument(parser)
     resume.add_guard_arguments(parser)
     resume.add_clip_arguments(parser)
@@ -290,6 +340,23 @@ def build_config(parsed, rank, world, device):
         raise SystemExit("train_image_phase2: --ema-decay is not available in phase 2: the optimizer is re-created every epoch and the state file "
                          "is this script's own, so the average has nowhere to live yet (train phase 1 with it, or average afterwards)")
     recipe = resume.recipe_entries(parsed)
+    if parsed.dataset_dir:
+        if not device_replay:
+            raise SystemExit("train_image_phase2: --dataset_dir needs --replay device (the recorded frames stay on the GPU and the buffer holds indices "
+                             "into them; the host replay buffer stores frames)")
+        if parsed.synthetic is not None:
+            raise SystemExit("train_image_phase2: --dataset_dir and --synthetic exclude each other (the buffer is filled from the recorded frames)")
+        if parsed.rollout_frames < 0 or parsed.buffer_limit < 1:
+            raise SystemExit("train_image_phase2: --rollout_frames must not be negative and --buffer_limit must be positive")
+        if parsed.resident_reserve_gb is not None and parsed.resident_reserve_gb < 0:
+            raise SystemExit("--resident-reserve-gb must not be negative")
+    else:
+        given = [f for f, on in (("--rollout_frames", parsed.rollout_frames != 4000), ("--buffer_limit", parsed.buffer_limit != 100000),
+                                 ("--resident-reserve-gb", parsed.resident_reserve_gb is not None)) if on]
+        if given:
+            raise SystemExit("train_image_phase2: %s need%s --dataset_dir" % (", ".join(given), "s" if len(given) == 1 else ""))
+    if parsed.synthetic is None:
+        parsed.synthetic = 20000
     if not device_replay:
         given = [f for f, on in (("--augment", parsed.augment != "None"), ("--batch_aug", parsed.batch_aug != 1), ("--save_state", parsed.save_state),
                                  ("--resume", parsed.resume), ("--seed", parsed.seed is not None)) if on]
@@ -310,6 +377,11 @@ def build_config(parsed, rank, world, device):
     if device_replay:
         config.update(replay="device", augment=parsed.augment, aug_fix_iter=parsed.aug_fix_iter, batch_aug=parsed.batch_aug, lr=parsed.lr,
                       synthetic_frames=True)
+        if parsed.dataset_dir:
+            config.update(dataset_dir=parsed.dataset_dir, rollout_frames=int(parsed.rollout_frames), buffer_limit=int(parsed.buffer_limit),
+                          synthetic_frames=False)
+            if parsed.resident_reserve_gb is not None:
+                config["resident_reserve_gb"] = float(parsed.resident_reserve_gb)
         if parsed.seed is not None:
             torch.manual_seed(parsed.seed)
             config["seed"] = int(parsed.seed)
@@ -336,17 +408,26 @@ def train(config, parsed, on_epoch_end=None):
     trainer = NativeTrainer(net, teacher, parsed.batch_size * parsed.batch_aug, (3, 160, 384), device, phase=1, lr=parsed.lr, world_size=world,
                             camera=camera_struct(), **resume.trainer_kwargs(config))
     if config.get("replay") == "device":
-        buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
+        rollout = None
+        if config.get("dataset_dir"):
+            buf, rollout = dataset_buffer(config, trainer, seed=parsed.seed)
+        else:
+            buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
             buf.reseed(parsed.seed * 7919 + rank)
         aug = make_augmenter(config)
-        episode0, epoch0 = load_state_device(config, trainer, buf, aug)
+        episode0, epoch0 = load_state_device(config, trainer, buf, aug, rollout)
         for episode in range(episode0, int(parsed.max_episode)):
             t0 = time.time()
-            _train_device(buf, trainer, config, episode, aug, epoch0 if episode == episode0 else 0, on_epoch_end)
+            start = epoch0 if episode == episode0 else 0
+            if rollout is not None and start == 0:        # (resumed inside an episode: its rollout ran before the state was written)
+                rec = rollout.run()
+                bzu.log.scalar(rollout_frames=rec["frames"], rollout_admitted=rec["admitted"], rollout_refreshed=rec["refreshed"],
+                               rollout_evicted=rec["evicted"], buffer_size=rec["n"])
+            _train_device(buf, trainer, config, episode, aug, start, on_epoch_end, rollout)
             if rank == 0:
                 print("episode %d: %.1f s" % (episode, time.time() - t0))
-        return {"net": net, "buffer": buf, "trainer": trainer}
+        return {"net": net, "buffer": buf, "trainer": trainer, "rollout": rollout}
     buf = synthetic_buffer(parsed.synthetic // world, device, seed=rank)
     for episode in range(int(parsed.max_episode)):
         t0 = time.time()
