@@ -41,7 +41,8 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      lbc_waypoint_metrics_state, lbc_waypoint_metrics_state_bytes, lbc_waypoint_metrics_update (a new descriptor, a new record
  *      type, two new exports; nothing existing changed).  And the same way: lbc_agent_desc, lbc_agent_state,
  *      lbc_agent_state_bytes, lbc_agent_control, lbc_agent_reset (a new descriptor, a new record type, three new exports; nothing
- *      existing changed).
+ *      existing changed).  And the same way: lbc_rollout_decide, lbc_rollout_stage_u8 (two new exports, no descriptor and no record
+ *      type; nothing existing changed).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -665,6 +666,32 @@ int lbc_replay_gather_indirect_u8(const unsigned char* src, long long row_bytes,
 size_t lbc_replay_admit_workspace(int limit, int m);
 int lbc_replay_admit(float* weights, int* frame, int* cmd, float* speed, int* slot_of_frame, int F, int n, int limit, const float* cw, const int* cframe,
                      const int* ccmd, const float* cspeed, int m, void* workspace, size_t workspace_bytes, int* record, lbc_stream_t stream);
+
+/* The on-policy tick of phase 2 (reference training/train_image_phase2.py:61-149 rollout, :45-58 get_control): after both networks and both
+ * controllers have run for N agents, who drives is decided and what the agents saw is recorded on the device.  Both calls only enqueue on
+ * `stream`.  The split into two launches is deliberate: the cursors and the tick counter are read and advanced by the ONE workgroup of
+ * lbc_rollout_decide, never by the copy grid, whose late workgroups would otherwise see an advanced counter.
+ * lbc_rollout_decide: one launch of one workgroup, 1 <= N <= 1024.  Reads per agent the student controller's and the teacher controller's
+ *   row of 8 doubles (lbc_agent_control's output layout), weight [N] f32 (lbc_phase2_weight), speed [N], command_onehot [N][4], active [N]
+ *   (NULL = all active); from device memory *p_student (double), *tick (64-bit counter), cursor [N] i32, dropped [N] i32.  Active agent a:
+ *     u = hash3(seed ^ (unsigned)(tick >> 32), (unsigned)tick, a) / 2^32 in double (hash3 as under lbc_replay_sample); the applied control
+ *     is the student's iff u < *p_student, else the teacher's.  If 0 <= cursor[a] < capacity: slot[a] = a * capacity + cursor[a], that
+ *     slot's slot_cmd (1 + the index of the command's 1, the rule of lbc_agent_control), slot_speed and slot_weight are written, cursor[a]
+ *     advances.  Otherwise slot[a] = -1 and dropped[a] advances (the reference stops appending at episode_length, :137).
+ *   An inactive agent: slot[a] = -1, an all-zero row, cursor and dropped untouched.  One thread advances *tick by one.
+ *   out [N][16] doubles: 0-2 applied steer / throttle / brake; 3 who (1 student, 0 teacher); 4 weight; 5 staged count after the tick;
+ *   6, 7 the student's and the teacher's controller flags; 8-10 the student's controls; 11-13 the teacher's; 14 dropped this tick (0 / 1);
+ *   15 zero.  slot_cmd / slot_speed / slot_weight hold N * capacity entries.  Double arithmetic, no atomics.
+ * lbc_rollout_stage_u8: for every agent with 0 <= slot[a] < stage_rows, row a of rgb (rgb_row_bytes each) and row a of birdview go to row
+ *   slot[a] of rgb_stage and birdview_stage; both kinds in one launch, 16 bytes per lane.  Reads nothing lbc_rollout_decide advances.
+ * LBC_EINVAL with a message and nothing launched: a NULL pointer (but active), N outside [1, 1024], capacity < 1 or N * capacity >= 2^31,
+ *   stage_rows < 1, row bytes that are not positive multiples of 16, frames or staging arrays that are not 16-byte aligned, doubles and the
+ *   counter not 8-byte aligned. */
+int lbc_rollout_decide(const double* student, const double* teacher, const float* weight, const float* speed, const float* command_onehot,
+                       const unsigned char* active, int N, int capacity, unsigned seed, const double* p_student, unsigned long long* tick,
+                       int* cursor, int* dropped, int* slot, int* slot_cmd, float* slot_speed, float* slot_weight, double* out, lbc_stream_t stream);
+int lbc_rollout_stage_u8(const unsigned char* rgb, long long rgb_row_bytes, const unsigned char* birdview, long long birdview_row_bytes, const int* slot,
+                         int N, long long stage_rows, unsigned char* rgb_stage, unsigned char* birdview_stage, lbc_stream_t stream);
 
 /* Device-resident LMDB dataset (bird_view/utils/datasets/resident.py): the per-sample work of the host loader -- frame look-up, crop or
  * rotation of the bird-view map, waypoints -- over a batch of frames that live in HBM.  The host draws and uploads one record of four

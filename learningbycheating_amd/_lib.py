@@ -207,6 +207,8 @@ _SIGNATURES = {
     "lbc_replay_scatter_u8": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
     "lbc_replay_meta": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "lbc_replay_writeback": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "lbc_rollout_decide": (c_int, [c_void_p] * 6 + [c_int, c_int, ctypes.c_uint] + [c_void_p] * 10),
+    "lbc_rollout_stage_u8": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong] + [c_void_p] * 3),
     "lbc_dataset_gather_crop_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p]),
     "lbc_dataset_gather_warp_crop_u8": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
     "lbc_dataset_targets": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p]),

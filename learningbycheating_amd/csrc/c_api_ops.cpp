@@ -318,6 +318,21 @@ int lbc_replay_writeback(const float* w_batch, const int* idx, int B, int reps, 
     return lbc_replay_writeback_launch(w_batch, idx, B, reps, n, new_w, (hipStream_t)stream);
 }
 
+// ---- the on-policy tick of phase 2 ----------------------------------------------------------------------------
+int lbc_rollout_decide(const double* student, const double* teacher, const float* weight, const float* speed, const float* command_onehot,
+                       const unsigned char* active, int N, int capacity, unsigned seed, const double* p_student, unsigned long long* tick,
+                       int* cursor, int* dropped, int* slot, int* slot_cmd, float* slot_speed, float* slot_weight, double* out, lbc_stream_t stream)
+{
+    return lbc_rollout_decide_launch(student, teacher, weight, speed, command_onehot, active, N, capacity, seed, p_student, tick, cursor, dropped, slot,
+                                     slot_cmd, slot_speed, slot_weight, out, (hipStream_t)stream);
+}
+
+int lbc_rollout_stage_u8(const unsigned char* rgb, long long rgb_row_bytes, const unsigned char* birdview, long long birdview_row_bytes, const int* slot,
+                         int N, long long stage_rows, unsigned char* rgb_stage, unsigned char* birdview_stage, lbc_stream_t stream)
+{
+    return lbc_rollout_stage_launch(rgb, rgb_row_bytes, birdview, birdview_row_bytes, slot, N, stage_rows, rgb_stage, birdview_stage, (hipStream_t)stream);
+}
+
 // ---- device-resident LMDB dataset ------------------------------------------------------------------------------
 int lbc_dataset_gather_crop_u8(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
                                unsigned char* dst, lbc_stream_t stream)

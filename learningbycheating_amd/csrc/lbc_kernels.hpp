@@ -251,6 +251,13 @@ int lbc_replay_scatter_launch(const unsigned char* src, long long row_bytes, con
 int lbc_replay_meta_launch(const float* speed, const int* cmd, const int* idx, int B, int reps, float* speed_out, float* onehot_out, hipStream_t s);
 int lbc_replay_writeback_launch(const float* w_batch, const int* idx, int B, int reps, int n, float* new_w, hipStream_t s);
 
+// ---- the on-policy tick of phase 2 (rollout.hip): who drives, and the record of what the agents saw ------------
+int lbc_rollout_decide_launch(const double* student, const double* teacher, const float* weight, const float* speed, const float* command_onehot,
+                              const unsigned char* active, int N, int capacity, unsigned seed, const double* p_student, unsigned long long* tick,
+                              int* cursor, int* dropped, int* slot, int* slot_cmd, float* slot_speed, float* slot_weight, double* out, hipStream_t s);
+int lbc_rollout_stage_launch(const unsigned char* rgb, long long rgb_row_bytes, const unsigned char* birdview, long long birdview_row_bytes, const int* slot, int N,
+                             long long stage_rows, unsigned char* rgb_stage, unsigned char* birdview_stage, hipStream_t s);
+
 // ---- device-resident LMDB dataset (dataset.hip) ------------------------------------------------------------
 int lbc_dataset_gather_crop_launch(const unsigned char* src, const int* idx, int B, int reps, int SH, int SW, int C, int y0, int x0, int H, int W,
                                    unsigned char* dst, hipStream_t s);

@@ -17,9 +17,16 @@ the next epoch bit for bit.
 and every episode begins with an offline rollout (training/rollout.py): --rollout_frames recorded frames are scored with the current
 student against the teacher, both in eval mode, and admitted into a buffer of --buffer_limit slots that holds frame indices into the
 resident dataset (lbc_replay_admit keeps the highest weights).  Then the epochs above run on it.  The states are the recorded ones, not
-the student's own: this is loss-prioritised replay over the dataset, the learner half of DAgger without its on-policy data."""
+the student's own: this is loss-prioritised replay over the dataset, the learner half of DAgger without its on-policy data.
+
+--env MODULE:FACTORY (with --replay device) is the on-policy loop: FACTORY(n_envs=, rank=, world=, **--env_kwargs) builds an object of the
+environment protocol (training/rollout.py; `--env synthetic` is the toy training/envs.py SyntheticEnv), and every episode begins with
+OnlineRollout.run(episode): the student drives --n_envs environments with the reference's mixing schedule (--beta), the teacher labels the
+same states, and --episode_length frames per environment go into a copying buffer of --buffer_limit slots (teaching.TeachingSession; the
+tick, the scoring and the recording stay on the device).  Then the epochs above run on it."""
 import argparse
 import ctypes
+import json
 import time
 from pathlib import Path
 
@@ -189,6 +196,25 @@ def _state_path(config):
     return resume._path(config["log_dir"], config["rank"])
 
 
+def online_rollout(config, trainer, seed=None):
+    """--env: the environments of this rank, the session that drives them on the trainer's own engines, an empty copying buffer of this
+    rank's share of --buffer_limit slots.  -> (buffer, rollout)"""
+    import importlib
+    from ..teaching import TeachingSession
+    from .rollout import OnlineRollout
+    rank, world, device = config["rank"], config["world_size"], config["device"]
+    if config["env"] == "synthetic":
+        from .envs import SyntheticEnv as factory
+    else:
+        module, _, name = config["env"].partition(":")
+        factory = getattr(importlib.import_module(module), name)
+    env = factory(n_envs=config["n_envs"], rank=rank, world=world, **config["env_kwargs"])
+    session = TeachingSession(trainer.student, trainer.teacher, device, config["n_envs"], config["episode_length"], camera=trainer.cam,
+                              seed=(0 if seed is None else int(seed)) * 7919 + rank)
+    buf = DeviceReplayBuffer(device, buffer_limit=max(1, config["buffer_limit"] // world), seed=rank)
+    return buf, OnlineRollout(session, buf, env, config["episode_length"], beta=config["beta"])
+
+
 def save_state_device(config, net, replay_buffer, augmenter, episode, epoch, rollout=None):
     """train_state.th (rank 0; train_state.rank%d.th on the others) after epoch `epoch` of episode `episode`.  The optimizer is
     re-created at every epoch, so there are no moments to keep; synthetic frames are a function of the seed and are not written.
@@ -202,6 +228,9 @@ def save_state_device(config, net, replay_buffer, augmenter, episode, epoch, rol
             "rng": {"cpu": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device)}}
     if rollout is not None:
         part["rollout"] = rollout.state_dict()
+    if config.get("env") and config["rank"] == 0:
+        frames = sum(part["buffer"][k].numel() for k in ("rgb", "birdview") if k in part["buffer"])
+        print("train_state: the replay buffer is written with its %d frames, %d bytes" % (part["buffer"]["n"], frames))
     if config["rank"] == 0:
         part["student"] = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     resume._atomic_save(part, _state_path(config))
@@ -238,7 +267,7 @@ def load_state_device(config, trainer, replay_buffer, augmenter, rollout=None):
         if (mine["aug"] is None) != (augmenter is None):
             raise ValueError("the state was saved %s augmentation, this run has %s" % (("without", "with") if mine["aug"] is None else ("with", "without")))
         if (mine.get("rollout") is None) != (rollout is None):
-            raise ValueError("the state was saved %s --dataset_dir, this run is %s it" % (("without", "with") if rollout is not None else ("with", "without")))
+            raise ValueError("the state was saved %s a rollout (--dataset_dir / --env), this run is %s one" % (("without", "with") if rollout is not None else ("with", "without")))
         replay_buffer.load_state_dict(mine["buffer"])
         if rollout is not None:
             rollout.load_state_dict(mine["rollout"])
@@ -258,7 +287,7 @@ def _epoch_steps(replay_buffer, config):
     """whole batches in the buffer.  With --dataset_dir under several ranks the buffers fill at their own pace (a rank's rollout refreshes
     what ITS buffer holds), and every step is a collective: all ranks take the smallest count."""
     steps = len(replay_buffer) // config["batch_size"]
-    if config.get("dataset_dir") and config.get("world_size", 1) > 1:
+    if (config.get("dataset_dir") or config.get("env")) and config.get("world_size", 1) > 1:
         least = torch.tensor([steps], dtype=torch.int64, device=config["device"])
         dist.all_reduce(least, op=dist.ReduceOp.MIN)
         steps = int(least)
@@ -313,6 +342,14 @@ def parse_arguments(argv=None):
     parser.add_argument("--rollout_frames", type=int, default=4000,
                         help="with --dataset_dir: frames scored per episode, over all ranks (0 = the whole dataset; the reference: 4 weathers x 1000)")
     parser.add_argument("--buffer_limit", type=int, default=100000, help="with --dataset_dir: slots of the replay buffer, over all ranks")
+    parser.add_argument("--env", default=None, metavar="MODULE:FACTORY",
+                        help="with --replay device: on-policy phase 2.  FACTORY(n_envs=, rank=, world=, **env_kwargs) builds the environments (the protocol "
+                             "is in training/rollout.py; 'synthetic' = the toy SyntheticEnv); every episode begins with a rollout in which the student "
+                             "drives, the teacher labels and --episode_length frames per environment go into a buffer of --buffer_limit slots")
+    parser.add_argument("--env_kwargs", default=None, metavar="JSON", help="with --env: keyword arguments of the factory, a JSON object")
+    parser.add_argument("--n_envs", type=int, default=1, help="with --env: environments per rank, driven in one batch")
+    parser.add_argument("--episode_length", type=int, default=1000, help="with --env: frames recorded per environment and episode")
+    parser.add_argument("--beta", type=float, default=0.95, help="with --env: P(student drives) = 0.5 + 0.5 (1 - beta^episode)")
     parser.add_argument("--resident-reserve-gb", type=float, default=None, metavar="GB",
                         help="with --dataset_dir: device memory to leave free for networks and workspaces (default: what batch 256 in fp32 needs)")
     loop.add_precision_argument(parser)
@@ -340,6 +377,30 @@ def build_config(parsed, rank, world, device):
         raise SystemExit("train_image_phase2: --ema-decay is not available in phase 2: the optimizer is re-created every epoch and the state file "
                          "is this script's own, so the average has nowhere to live yet (train phase 1 with it, or average afterwards)")
     recipe = resume.recipe_entries(parsed)
+    env_kwargs = {}
+    if parsed.env:
+        if not device_replay:
+            raise SystemExit("train_image_phase2: --env needs --replay device (the tick records its frames on the GPU and commits them to the device "
+                             "replay buffer)")
+        if parsed.dataset_dir:
+            raise SystemExit("train_image_phase2: --env and --dataset_dir exclude each other (on-policy frames or recorded ones)")
+        if parsed.synthetic is not None:
+            raise SystemExit("train_image_phase2: --env and --synthetic exclude each other (the buffer is filled by the rollout)")
+        if parsed.env != "synthetic" and not (parsed.env.count(":") == 1 and all(parsed.env.split(":"))):
+            raise SystemExit("train_image_phase2: --env is MODULE:FACTORY or 'synthetic', got %r" % parsed.env)
+        try:
+            env_kwargs = json.loads(parsed.env_kwargs) if parsed.env_kwargs else {}
+        except ValueError as e:
+            raise SystemExit("train_image_phase2: --env_kwargs is not JSON: %s" % e)
+        if not isinstance(env_kwargs, dict):
+            raise SystemExit("train_image_phase2: --env_kwargs must be a JSON object")
+        if not 1 <= parsed.n_envs <= 1024 or parsed.episode_length < 1 or parsed.buffer_limit < 1 or not 0.0 <= parsed.beta <= 1.0:
+            raise SystemExit("train_image_phase2: --n_envs must lie in 1..1024, --episode_length and --buffer_limit must be positive, --beta in [0, 1]")
+    else:
+        given = [f for f, on in (("--env_kwargs", parsed.env_kwargs is not None), ("--n_envs", parsed.n_envs != 1),
+                                 ("--episode_length", parsed.episode_length != 1000), ("--beta", parsed.beta != 0.95)) if on]
+        if given:
+            raise SystemExit("train_image_phase2: %s need%s --env" % (", ".join(given), "s" if len(given) == 1 else ""))
     if parsed.dataset_dir:
         if not device_replay:
             raise SystemExit("train_image_phase2: --dataset_dir needs --replay device (the recorded frames stay on the GPU and the buffer holds indices "
@@ -351,7 +412,7 @@ def build_config(parsed, rank, world, device):
         if parsed.resident_reserve_gb is not None and parsed.resident_reserve_gb < 0:
             raise SystemExit("--resident-reserve-gb must not be negative")
     else:
-        given = [f for f, on in (("--rollout_frames", parsed.rollout_frames != 4000), ("--buffer_limit", parsed.buffer_limit != 100000),
+        given = [f for f, on in (("--rollout_frames", parsed.rollout_frames != 4000), ("--buffer_limit", parsed.buffer_limit != 100000 and not parsed.env),
                                  ("--resident-reserve-gb", parsed.resident_reserve_gb is not None)) if on]
         if given:
             raise SystemExit("train_image_phase2: %s need%s --dataset_dir" % (", ".join(given), "s" if len(given) == 1 else ""))
@@ -382,6 +443,9 @@ def build_config(parsed, rank, world, device):
                           synthetic_frames=False)
             if parsed.resident_reserve_gb is not None:
                 config["resident_reserve_gb"] = float(parsed.resident_reserve_gb)
+        if parsed.env:
+            config.update(env=parsed.env, env_kwargs=env_kwargs, n_envs=int(parsed.n_envs), episode_length=int(parsed.episode_length),
+                          beta=float(parsed.beta), buffer_limit=int(parsed.buffer_limit), synthetic_frames=False)
         if parsed.seed is not None:
             torch.manual_seed(parsed.seed)
             config["seed"] = int(parsed.seed)
@@ -411,6 +475,8 @@ def train(config, parsed, on_epoch_end=None):
         rollout = None
         if config.get("dataset_dir"):
             buf, rollout = dataset_buffer(config, trainer, seed=parsed.seed)
+        elif config.get("env"):
+            buf, rollout = online_rollout(config, trainer, seed=parsed.seed)
         else:
             buf = synthetic_buffer_device(parsed.synthetic // world, device, seed=rank)
         if parsed.seed is not None:                       # (unseeded: the streams of the frames' seed, as the host buffer)
@@ -420,7 +486,11 @@ def train(config, parsed, on_epoch_end=None):
         for episode in range(episode0, int(parsed.max_episode)):
             t0 = time.time()
             start = epoch0 if episode == episode0 else 0
-            if rollout is not None and start == 0:        # (resumed inside an episode: its rollout ran before the state was written)
+            if rollout is not None and start == 0 and config.get("env"):
+                rec = rollout.run(episode)
+                bzu.log.scalar(rollout_frames=rec["frames"], rollout_ticks=rec["ticks"], rollout_student_share=rec["student_share"],
+                               rollout_collisions=rec["collisions"], rollout_skipped_nonfinite=rec["skipped_nonfinite"], buffer_size=rec["n"])
+            elif rollout is not None and start == 0:      # (resumed inside an episode: its rollout ran before the state was written)
                 rec = rollout.run()
                 bzu.log.scalar(rollout_frames=rec["frames"], rollout_admitted=rec["admitted"], rollout_refreshed=rec["refreshed"],
                                rollout_evicted=rec["evicted"], buffer_size=rec["n"])
