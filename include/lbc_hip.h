@@ -42,7 +42,8 @@ const char* lbc_backend(void);   /* "hip-gfx950" for the product library */
  *      type, two new exports; nothing existing changed).  And the same way: lbc_agent_desc, lbc_agent_state,
  *      lbc_agent_state_bytes, lbc_agent_control, lbc_agent_reset (a new descriptor, a new record type, three new exports; nothing
  *      existing changed).  And the same way: lbc_rollout_decide, lbc_rollout_stage_u8 (two new exports, no descriptor and no record
- *      type; nothing existing changed).
+ *      type; nothing existing changed).  And the same way: lbc_visuals_desc, lbc_visuals_image_shape, lbc_visuals_render (a new
+ *      descriptor, two new exports, no record type; nothing existing changed).
  * The size_t-returning *_workspace() queries and the int-returning *_supported() queries answer 0 for "none / no" AND for a refused
  * descriptor: a host that gets 0 checks lbc_last_error() (empty = a genuine 0), as tests/c_host/host.c does. */
 #define LBC_HIP_ABI_VERSION 201
@@ -423,6 +424,58 @@ typedef struct lbc_waypoint_metrics_state {      /* 248 fields of 8 bytes; [c] c
 size_t lbc_waypoint_metrics_state_bytes(void);
 int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const float* pred, const float* target, const float* command_onehot,
                                 const float* loss /* may be NULL */, int N, void* state, lbc_stream_t stream);
+
+/* Training visuals on the device (csrc/visuals.hip): the grid of waypoint panels the reference's _log_visuals draws on the host
+ * (training/train_image_phase0.py:91-147, train_image_phase1.py:72-128, train_birdview.py:57-99), rendered by ONE launch into a uint8
+ * image [rows][cols][3] in device memory, from the tensors the loss launch has just read.  Nothing is read back by the library.
+ * mode 0: phase 0; 1: phases 1 and 2; 2: bird-view.  pred / teacher_or_target are [N][5][2] f32 (modes 0, 2) or [N][4][5][2] (mode 1,
+ * where the branch c = the first non-zero entry of command_onehot[n] is drawn, and no dot at all when the row is all zero).
+ * Panel: modes 0 and 1, BH rows x (W + BW) columns -- the camera frame at rows (BH - H) / 2 .. + H - 1, columns 0 .. W - 1, black above
+ *   and below it, the map canvas (BH x BW) at columns W .. W + BW - 1; mode 2, the canvas alone.  Nothing is resampled (the reference
+ *   shrinks the canvas to the frame's height with cv2.resize).
+ * Canvas: (0, 47, 0); then for channel i = 0..6 a pixel whose bird-view channel i is > 0 takes the reference's COLORS[i] (the highest set
+ *   channel wins).  birdview is [N][BH][BW][7] u8 or, birdview_f32 != 0, [N][7][BH][BW] f32; NULL (modes 0 and 1): background only.
+ * Frame: rgb [N][H][W][3] u8 as it is, or, rgb_f32 != 0, [N][3][H][W] f32 in [0, 1] as (uint8)(x * 255.0f) (f32 product, truncated).
+ * Dots: 5 x 5 squares, rows int(y) - 2 .. int(y) + 2, columns int(x) - 2 .. int(x) + 2 (int truncates toward zero), clipped to their
+ *   canvas or frame; a dot with a coordinate that is not finite or has |v| >= 2^30 is not drawn; a later dot covers an earlier one.
+ *   All coordinates in DOUBLE from the f32 inputs, with f = w / (2 tan(fov pi / 360)) computed on the host:
+ *   canvas, modes 0 and 1: teacher BLUE (0, 0, 255) at (t + 1) crop_size / 2; then, mode 1, the student RED (255, 0, 0) unprojected as
+ *     under lbc_waypoint_metrics_update, pred_frame 0.
+ *   frame, mode 0: teacher BLUE projected -- (px, py) = (t + 1) crop_size / 2, X = (px - crop_size / 2) / pixels_per_meter,
+ *     Z = (crop_size - py) / pixels_per_meter + fixed_offset, u = f X / Z + w / 2, v = f world_y / Z + h / 2, clipped to [0, w] x [0, h]
+ *     (a NaN stays a NaN); then, modes 0 and 1, the student RED at ((x + 1) w / 2, (y + 1) h / 2).
+ *   canvas, mode 2: the ground truth BLUE at its pixel coordinates, then the prediction RED at (p + 1) crop_size / 2.
+ *   (The reference's white marker at (0, 0) is an empty slice there and is left out.)
+ * Text: white, on the canvas, over the dots: "Command: LEFT|RIGHT|STRAIGHT|FOLLOW" ("???" for an all-zero row) and "Loss: " + the
+ *   per-sample loss as '%.2f' prints it (c = rint(v 100) in double, which is exact for an f32 v; "nan", "inf", "-inf").  Glyphs 5 x 7 from
+ *   `font` (95 x 7 bytes, ASCII 32..126, bit 4 of a row byte = the left column), advance 6; line k = 1, 2 occupies canvas rows
+ *   19 k - 6 .. 19 k from canvas column 0 and is cut at the canvas edge.
+ * Selection: the candidates are samples 0 .. min(N, size) - 1.  sort != 0: panel slot k shows the candidate of rank k by loss,
+ *   descending, ties by lower index first, a NaN before everything; sort == 0: slot k is sample k.
+ * Grid: ncols panels per row, 2 black pixels around and between panels, unused slots of the last row black; rows = 2 +
+ *   ceil(min(N, size) / ncols) (BH + 2), cols = 2 + ncols (panel columns + 2).  EVERY byte of the image is written by every launch,
+ *   each exactly once: no atomics, and the same inputs give the same bytes.  No min / max normalisation (make_grid's normalize=True).
+ * Refused with LBC_EINVAL (nothing launched, nothing written): a struct_size other than sizeof(lbc_visuals_desc) (start it as
+ *   `lbc_visuals_desc d = LBC_VISUALS_DESC_INIT;`), an unknown mode, size outside 1..32, ncols < 1, N < 1, BH / BW / W outside 1..16384,
+ *   H outside 1..BH (modes 0, 1), an image of 2^29 pixels or more, a NULL rgb (modes 0, 1), pred, teacher_or_target, command_onehot, loss,
+ *   font or out, a NULL birdview in mode 2, an out that is not 4-byte aligned. */
+typedef struct lbc_visuals_desc {
+    unsigned struct_size;        /* = sizeof(lbc_visuals_desc) */
+    lbc_camera camera;
+    int mode;                    /* 0, 1, 2 */
+    int size;                    /* panels at most: 1..32 */
+    int sort;                    /* != 0: by loss, descending */
+    int ncols;                   /* panels per grid row */
+    int N;                       /* samples in the batch */
+    int H, W;                    /* camera frame (modes 0, 1) */
+    int BH, BW;                  /* map canvas */
+    int rgb_f32, birdview_f32;   /* != 0: that tensor is f32 NCHW instead of u8 NHWC */
+} lbc_visuals_desc;
+#define LBC_VISUALS_DESC_INIT { (unsigned)sizeof(lbc_visuals_desc), { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, 0, 8, 0, 4, 0, 0, 0, 0, 0, 0, 0 }
+int lbc_visuals_image_shape(const lbc_visuals_desc* desc, int* rows, int* cols);
+int lbc_visuals_render(const lbc_visuals_desc* desc, const void* rgb, const void* birdview /* may be NULL */, const float* pred,
+                       const float* teacher_or_target, const float* command_onehot, const float* loss, const unsigned char* font,
+                       unsigned char* out, lbc_stream_t stream);
 
 /* The agent half of the tick on the device (csrc/agent.hip): waypoints -> steer / throttle / brake for N independent agents in one
  * launch, the controller state kept in device memory.  Restates the arithmetic of the reference's two agents and their controllers

@@ -109,6 +109,17 @@ class WaypointMetricsState(ctypes.Structure):
                 ("loss_sum", ctypes.c_double), ("loss_bad", ctypes.c_longlong)]
 
 
+class VisualsDesc(ctypes.Structure):
+    """lbc_visuals_desc (a host struct, read during the call); struct_size is filled in here and the defaults are LBC_VISUALS_DESC_INIT's"""
+    _fields_ = ([("struct_size", ctypes.c_uint), ("camera", Camera)] +
+                [(n, c_int) for n in ("mode", "size", "sort", "ncols", "N", "H", "W", "BH", "BW", "rgb_f32", "birdview_f32")])
+
+    def __init__(self, **kw):
+        d = dict(struct_size=ctypes.sizeof(VisualsDesc), size=8, ncols=4)
+        d.update(kw)
+        super().__init__(**d)
+
+
 class AgentDesc(ctypes.Structure):
     """lbc_agent_desc (a host struct, read during the call); struct_size is filled in here, everything else by agent.ControllerConfig"""
     _fields_ = ([("struct_size", ctypes.c_uint), ("kind", c_int), ("n_steps", c_int), ("speed_steps", c_int)] +
@@ -177,6 +188,8 @@ _SIGNATURES = {
     "lbc_grad_accumulate": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
     "lbc_waypoint_metrics_state_bytes": (c_size_t, []),
     "lbc_waypoint_metrics_update": (c_int, [ctypes.POINTER(WaypointMetricsDesc)] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
+    "lbc_visuals_image_shape": (c_int, [ctypes.POINTER(VisualsDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lbc_visuals_render": (c_int, [ctypes.POINTER(VisualsDesc)] + [c_void_p] * 9),
     "lbc_agent_state_bytes": (c_size_t, [c_int]),
     "lbc_agent_control": (c_int, [ctypes.POINTER(AgentDesc)] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_void_p]),
     "lbc_agent_reset": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

@@ -47,7 +47,15 @@ class Experiment(object):
             self.scalars.setdefault((is_train, k), []).append(float(v))
 
     def image(self, is_train=True, **kwargs):
-        pass   # visualisation (cv2) is outside the hot path
+        """every (H, W, 3) uint8 array -> log_dir/visuals/<train|val>_<key>_<epoch:03d>.png, on rank 0 (training/visuals.py renders the
+        grid on the device and writes the file with the standard library; the reference hands a list of cv2 canvases to tensorboardX)"""
+        if self.rank != 0:
+            return
+        from ...training.visuals import write_png
+        out = self.log_dir / "visuals"
+        out.mkdir(parents=True, exist_ok=True)
+        for k, v in sorted(kwargs.items()):
+            write_png(out / ("%s_%s_%03d.png" % ("train" if is_train else "val", k, self.epoch)), v)
 
     def end_epoch(self, net=None):
         rec = {"epoch": self.epoch, "time": time.time()}

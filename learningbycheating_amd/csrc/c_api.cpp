@@ -67,6 +67,16 @@ int lbc_waypoint_metrics_update(const lbc_waypoint_metrics_desc* desc, const flo
     return lbc_waypoint_metrics_launch(desc, pred, target, command_onehot, loss, N, state, (hipStream_t)stream);
 }
 
+int lbc_visuals_image_shape(const lbc_visuals_desc* desc, int* rows, int* cols) { return lbc_visuals_shape(desc, rows, cols); }
+
+int lbc_visuals_render(const lbc_visuals_desc* desc, const void* rgb, const void* birdview, const float* pred, const float* teacher_or_target,
+                       const float* command_onehot, const float* loss, const unsigned char* font, unsigned char* out, lbc_stream_t stream)
+{
+    static_assert(sizeof(lbc_visuals_desc) == 76 && offsetof(lbc_visuals_desc, camera) == 4 && offsetof(lbc_visuals_desc, mode) == 32 &&
+                  offsetof(lbc_visuals_desc, N) == 48 && offsetof(lbc_visuals_desc, birdview_f32) == 72, "lbc_visuals_desc layout (include/lbc_hip.h)");
+    return lbc_visuals_launch(desc, rgb, birdview, pred, teacher_or_target, command_onehot, loss, font, out, (hipStream_t)stream);
+}
+
 size_t lbc_agent_state_bytes(int n_agents) { return n_agents > 0 ? sizeof(lbc_agent_state) * (size_t)n_agents : 0; }
 
 int lbc_agent_control(const lbc_agent_desc* desc, const float* pred, const float* speed, const float* command_onehot,

@@ -310,6 +310,12 @@ int lbc_grad_accumulate_launch(const float* g, float* acc, long long n, int firs
 struct lbc_waypoint_metrics_desc;
 int lbc_waypoint_metrics_launch(const lbc_waypoint_metrics_desc* d, const float* pred, const float* target, const float* command_onehot,
                                 const float* loss, int N, void* state, hipStream_t s);
+// visuals.hip: one launch renders the grid of waypoint panels (frame, coloured bird-view, dots, command and loss text) into a uint8 HWC
+// image in device memory; a gather, every byte written once, no atomics.  The descriptor is validated there.
+struct lbc_visuals_desc;
+int lbc_visuals_shape(const lbc_visuals_desc* d, int* rows, int* cols);
+int lbc_visuals_launch(const lbc_visuals_desc* d, const void* rgb, const void* birdview, const float* pred, const float* teacher,
+                       const float* command_onehot, const float* loss, const unsigned char* font, unsigned char* out, hipStream_t s);
 // agent.hip: waypoints -> steer / throttle / brake for N agents in one launch, one thread per agent, the two PID windows in the device
 // records lbc_agent_state (include/lbc_hip.h); double arithmetic, no atomics.  The descriptor is validated here.
 struct lbc_agent_desc;

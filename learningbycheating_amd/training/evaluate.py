@@ -3,7 +3,8 @@
 The pass is the training scripts' validation pass with --val-metrics: non-updating eval-mode steps (NativeTrainer.step(update=False,
 train_mode=False, metrics=m)) that add every batch's waypoint errors in metres into one device record, one read-back after the
 last batch.  No optimizer step, no updating step.  Prints WaypointMetrics.result() as one JSON line and writes it to metrics.json
-beside the checkpoint (model-N.th and model-ema-N.th are both plain state_dicts of the student)."""
+beside the checkpoint (model-N.th and model-ema-N.th are both plain state_dicts of the student).  --visuals also draws every batch's
+waypoint panels on the device (training/visuals.py) and writes the last grid as visuals.png beside metrics.json."""
 import argparse
 import json
 import os
@@ -20,14 +21,16 @@ from .native import NativeTrainer, camera_struct
 PHASES = {"0": 0, "1": 1, "birdview": "birdview"}
 
 
-def validation_pass(trainer, data, device, metrics=None, max_batches=None):
+def validation_pass(trainer, data, device, metrics=None, max_batches=None, visuals=None):
     """one pass over `data` without updates, in eval mode, feeding `metrics` (default: a fresh object that fits the trainer's phase);
-    nothing is read back inside the loop.  -> the metrics object"""
+    nothing is read back inside the loop.  visuals: a PanelRenderer that draws every batch's panels (one more launch each; its last
+    grid is the caller's to read).  -> the metrics object"""
     m = metrics if metrics is not None else trainer.make_metrics()
+    draw = {} if visuals is None else {"visuals": visuals}
     for i, batch in enumerate(data):
         if max_batches is not None and i >= max_batches:
             break
-        loop.step_batch(trainer, batch, device, update=False, train_mode=False, metrics=m)
+        loop.step_batch(trainer, batch, device, update=False, train_mode=False, metrics=m, **draw)
     return m
 
 
@@ -73,7 +76,9 @@ def main(argv=None):
     parser.add_argument("--fixed_offset", type=float, default=4.0)
     loop.add_precision_argument(parser)
     resume.add_resident_arguments(parser)
+    resume.add_visuals_arguments(parser)
     parsed = parser.parse_args(argv)
+    draw = resume.visuals_entries(parsed)
     resident = resume.resident_entries(parsed, teacher=parsed.phase != "birdview")
     _, _, local = loop.ranks()
     device = loop.select_device(local, "evaluation")
@@ -87,7 +92,11 @@ def main(argv=None):
     _, data_val = make_loaders(config, device, teacher=teacher)      # (--cache-teacher: the loaders run the teacher, once per frame)
     trainer = build_trainer(phase, parsed.model_path, parsed.teacher_path, parsed.batch_size, parsed.precision, device, parsed.fixed_offset,
                             networks=(net, resume.teacher_for_trainer(config, teacher)))
-    res = validation_pass(trainer, data_val, device).result()
+    visuals = trainer.make_visuals(size=draw.get("visuals_size")) if draw else None
+    res = validation_pass(trainer, data_val, device, visuals=visuals).result()
+    if visuals is not None and visuals.rendered:
+        from .visuals import write_png
+        write_png(Path(parsed.model_path).parent / "visuals.png", visuals.image())      # (--visuals: the last batch's panels)
     res.update(model_path=str(parsed.model_path), phase=parsed.phase, precision=parsed.precision)
     res["within"] = {"%g" % k: v for k, v in res["within"].items()}
     line = json.dumps(res)

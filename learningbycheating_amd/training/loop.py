@@ -69,6 +69,7 @@ def add_common_arguments(parser, max_epoch, batch_size):
     parser.add_argument("--synthetic", type=int, default=2048, help="number of device-resident synthetic frames (used when no --dataset_dir is given)")
     parser.add_argument("--iters_per_epoch", type=int, default=1000)
     add_precision_argument(parser)
+    resume.add_visuals_arguments(parser)
 
 
 # ---- one batch, one pass, the epochs -----------------------------------------------------------------------------------------------
@@ -94,11 +95,14 @@ def run_pass(spec, trainer, data, is_train, config, is_first_epoch, epoch=0, loa
     windows = resume.Windows(config, trainer, first)                 # (--accumulate: iterations stay loader iterations)
     metrics = resume.pass_metrics(config, trainer, is_train)         # (--val-metrics / --train-metrics; None without them)
     sync_free = metrics is not None and not is_train                 # the validation pass with --val-metrics reads nothing back per batch
+    visuals = resume.pass_visuals(config, trainer, is_train)         # (--visuals, rank 0; None without it)
     noise = config.get("speed_noise", 0) if is_train else 0
     for i, batch in enumerate(data, start=first):
-        loss = step_batch(trainer, batch, config["device"], noise, update=update, train_mode=is_train, metrics=metrics)
-        windows.after_step(update)
         should_log = (i % int(config["log_iterations"]) == 0) or (not is_train) or is_first_epoch
+        # (--visuals: a logging iteration's step carries the renderer -- one more launch, nothing read back)
+        draw = {"visuals": visuals} if (visuals is not None and should_log) else {}
+        loss = step_batch(trainer, batch, config["device"], noise, update=update, train_mode=is_train, metrics=metrics, **draw)
+        windows.after_step(update)
         if should_log and not sync_free:
             lm = loss.mean().item()          # device->host sync only when logging, as the reference (train_image_phase1.py:207-221)
             skipped = resume.check_skipped(config, trainer, spec.label) if is_train else None
@@ -126,6 +130,7 @@ def run_pass(spec, trainer, data, is_train, config, is_first_epoch, epoch=0, loa
         windows.end_pass(bzu.log.scalar, is_train=is_train)
     if sync_free:
         resume.log_val_metrics(config, metrics, bzu.log.scalar, nonfinite=spec.nonfinite and spec.nonfinite % ("validation loss", "%s"))
+    resume.log_visuals(visuals, bzu.log.image, is_train)             # (--visuals: the pass's one read-back of the last rendered grid)
 
 
 def run_epochs(spec, config, net, trainer, loaders, state):

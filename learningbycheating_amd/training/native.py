@@ -78,6 +78,13 @@ class NativeTrainer:
     step needs teacher_out; birdview= and teacher_out= together, or a teacher_out of the wrong shape, dtype or device, are refused with
     ValueError before anything is launched.
 
+    step(..., visuals=v) (training/visuals.py PanelRenderer; default None: the launches of a step are exactly what they were): right
+    behind the loss launch (and the metrics launch, if there is one), on their stream, one more launch draws this batch's panels --
+    camera frame, coloured bird-view, the teacher's waypoints in blue, the student's in red, command and per-sample loss as text -- into
+    v's device image.  It only reads what the loss read and wrote, and nothing is read back: `v.image()` is the copy.  `make_visuals()`
+    builds a renderer that fits this trainer's phase; one of another mode is refused with ValueError before anything is launched.
+    With teacher_out= there is no bird-view on the device: the canvas is background and dots.
+
     state_dict() / load_state_dict(): everything the trainer owns that a continued run needs -- see there."""
 
     def __init__(self, student, teacher, batch, image_shape, device, phase=1, lr=1e-4, world_size=1, group=None, camera=None, grad_dtype=None,
@@ -173,6 +180,18 @@ class NativeTrainer:
             raise ValueError("NativeTrainer.step: phase %r compares against target * %r + %r, the metrics object was built for target * %r + %r"
                              % (self.phase, scale, shift, metrics.target_scale, metrics.target_shift))
 
+    def _visuals_mode(self):
+        from .visuals import MODES
+        if self.phase not in MODES:
+            raise ValueError("NativeTrainer: phase %r has no panels to draw (phases 0, 1 and 'birdview' have)" % (self.phase,))
+        return MODES[self.phase]
+
+    def make_visuals(self, size=None, ncols=4):
+        """a training/visuals.py PanelRenderer that fits this trainer's phase; size / sort default to the reference's: 32 panels sorted by
+        loss in phase 0, 8 unsorted in phase 1, 16 sorted for the bird-view"""
+        from .visuals import PanelRenderer
+        return PanelRenderer(self.device, self.cam, self._visuals_mode(), size=size, ncols=ncols)
+
     def _check_teacher_out(self, teacher_out, birdview, n, device):
         """the refusals of step(teacher_out=...), before anything is launched -> (sel, all), the one this phase's loss reads packed"""
         if self.phase not in (0, 1):
@@ -191,7 +210,8 @@ class NativeTrainer:
         # (the loss takes a raw pointer to dense rows: the views a loader's teacher cache hands out have the cached row's pitch)
         return (sel, every.contiguous()) if self.phase == 1 else (sel.contiguous(), every)
 
-    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None, metrics=None, teacher_out=None):
+    def step(self, x, speed, command, birdview=None, target=None, update=True, train_mode=True, on_forward=None, metrics=None, teacher_out=None,
+             visuals=None):
         """x: student input, float32 (N,C,H,W) in [0,1] or the dataset's uint8 (N,H,W,C) frames; command one-hot (N,4);
         returns the per-sample loss (device tensor).  update=False: forward + loss only.  train_mode=False: the student runs
         in eval mode (running statistics, no buffer update) -- the reference's validation pass (train_image_phase1.py:162-165,256).
@@ -206,6 +226,9 @@ class NativeTrainer:
             raise RuntimeError("NativeTrainer.step: an updating step inside ema_weights() would train the average")
         if metrics is not None:
             self._check_metrics(metrics)
+        if visuals is not None and visuals.mode != self._visuals_mode():
+            raise ValueError("NativeTrainer.step: phase %r draws panels of mode %d, the renderer was built for mode %d"
+                             % (self.phase, self._visuals_mode(), visuals.mode))
         n = x.shape[0]
         if teacher_out is not None:
             teacher_out = self._check_teacher_out(teacher_out, birdview, n, x.device)
@@ -259,6 +282,15 @@ class NativeTrainer:
                 metrics.update(p_all, t_all if self.phase == 1 else target, command, self.loss[:n])
             else:
                 metrics.update(p_sel, t_sel if self.phase == 0 else target, command, self.loss[:n])
+        if visuals is not None:
+            # one more launch that only reads, behind the loss (and the metrics) on their stream: the frames and the waypoints the loss
+            # just read, the per-sample loss it just wrote.  With teacher_out= there is no bird-view: background and dots
+            if self.phase == "birdview":
+                visuals.render(None, x, p_sel, target, command, self.loss[:n])
+            elif self.phase == 1:
+                visuals.render(x, birdview, p_all, t_all, command, self.loss[:n])
+            else:
+                visuals.render(x, birdview, p_sel, t_sel, command, self.loss[:n])
         if update and self.accumulate > 1:
             self._accumulating_backward(d_sel, d_all)
         elif update:

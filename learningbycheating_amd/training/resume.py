@@ -1,6 +1,6 @@
 """The flags, config entries and state files of the options the training scripts share: --save_state / --resume / --skip-nonfinite /
 --clip-grad-norm / --log-grad-norm / --accumulate / --lr-schedule / --weight-decay / --ema-decay / --val-metrics / --train-metrics /
---resident / --cache-teacher.  Every option is declared here once (add_arguments), turned into config entries here (config_entries,
+--visuals / --resident / --cache-teacher.  Every option is declared here once (add_arguments), turned into config entries here (config_entries,
 resident_entries: a run without an option writes the config.json it always wrote) and read back here by what the loop calls on logging
 iterations and at epoch ends.  The loop itself -- the pass over a loader, the epochs, the launch -- is training/loop.py.
 
@@ -115,6 +115,49 @@ def metrics_entries(parsed):
     if getattr(parsed, "train_metrics", False):
         out["train_metrics"] = True
     return out
+
+
+def add_visuals_arguments(parser):
+    parser.add_argument("--visuals", action="store_true",
+                        help="draw the reference's waypoint panels (camera frame, coloured bird-view, teacher blue, student red, command and "
+                             "loss) on the device on every logging iteration -- one launch, nothing read back -- and write the last grid of "
+                             "every pass to log_dir/visuals/<train|val>_birdview_<epoch>.png.  Default: off")
+    parser.add_argument("--visuals-size", type=int, default=None, metavar="N",
+                        help="with --visuals: panels per grid, 1..32 (default: the reference's 32 / 8 / 16 for phase 0 / phase 1 / bird-view)")
+
+
+def visuals_entries(parsed):
+    """config entries of --visuals / --visuals-size; a run without them writes the config.json it always wrote"""
+    size = getattr(parsed, "visuals_size", None)
+    if not getattr(parsed, "visuals", False):
+        if size is not None:
+            raise SystemExit("--visuals-size needs --visuals")
+        return {}
+    if size is not None and not 1 <= size <= 32:
+        raise SystemExit("--visuals-size must lie in 1..32")
+    return {"visuals": True} if size is None else {"visuals": True, "visuals_size": int(size)}
+
+
+def pass_visuals(config, trainer, is_train):
+    """the PanelRenderer a pass hands to trainer.step on its logging iterations: with --visuals, on rank 0 (the rank that writes the
+    file); None otherwise (the step then launches what it always launched).  One object per trainer and kind, made on first use."""
+    if not config.get("visuals") or config.get("rank", 0) != 0:
+        return None
+    kept = trainer.__dict__.setdefault("_pass_visuals", {})
+    if is_train not in kept:
+        kept[is_train] = trainer.make_visuals(size=config.get("visuals_size"))
+    kept[is_train].rendered = 0
+    return kept[is_train]
+
+
+def log_visuals(visuals, log_image, is_train):
+    """the end of a pass with --visuals: if anything was rendered, ONE read-back of the last grid, handed to the logger as `birdview`
+    (the reference's key).  -> the array or None"""
+    if visuals is None or not visuals.rendered:
+        return None
+    img = visuals.image()
+    log_image(is_train=is_train, birdview=img)
+    return img
 
 
 def pass_metrics(config, trainer, is_train):
@@ -335,6 +378,7 @@ def config_entries(parsed):
     out.update(accumulate_entries(parsed))
     out.update(recipe_entries(parsed))
     out.update(metrics_entries(parsed))
+    out.update(visuals_entries(parsed))
     return out
 
 

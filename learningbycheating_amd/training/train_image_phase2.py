@@ -113,8 +113,9 @@ def _train(replay_buffer, trainer, config, episode):
                 _log_guard(trainer, config)
         windows.end_pass(bzu.log.scalar)
         replay_buffer.normalize_weights()
-        # the reference evaluates (eval mode) and visualises the 32 highest-weight samples here (:229-250); visualisation
-        # is outside the hot path, the forward is kept so that the same kernels run
+        # the reference evaluates (eval mode) and visualises the 32 highest-weight samples here (:229-250); this loop does not draw them
+        # (training/visuals.py PanelRenderer(mode=1, size=16) renders such panels on the device from a step's tensors), the forward is
+        # kept so that the same kernels run
         top, rgb, bv, cmd, speed = replay_buffer.get_highest_k(min(32, len(replay_buffer)))
         net.eval()
         with torch.no_grad():
