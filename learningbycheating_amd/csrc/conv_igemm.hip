@@ -24,6 +24,7 @@
 #include "lbc_common.hpp"
 #include "lbc_act.hpp"
 #include <type_traits>
+#include <assert.h>
 #include <stdlib.h>
 
 namespace {
@@ -539,7 +540,8 @@ int lbc_weight_prep(const WeightPrepArgs& a, hipStream_t s)
     return lbc_check_launch("weight_prep");
 }
 
-int lbc_igemm_rows(const IgemmArgs& a, int cfg)
+// number of M tiles (= stats rows) of a launch
+static int lbc_igemm_rows(const IgemmArgs& a, int cfg)
 {
     if (cfg >= kLbcCfgHdma) return lbc_conv_hdma_rows(a, cfg);
     if (cfg >= kLbcCfgGlds) return lbc_conv_glds_rows(a, cfg);
@@ -547,21 +549,22 @@ int lbc_igemm_rows(const IgemmArgs& a, int cfg)
     return lbc_cdiv(a.M, kCfgBM[cfg]);
 }
 
-bool lbc_igemm_fuses_bn_bwd(const IgemmArgs& a, int wmajor, int mode, int cfg)
+bool lbc_igemm_fuses_bn_bwd(const IgemmArgs& a, const IgemmPlan& p)
 {
-    if (lbc_opt_on(kOptNoBnBwdFuse) || mode != 1 || !a.act_bf16) return false;
-    if (cfg >= kLbcCfgGlds) return true;          // conv_glds2_k (lds_dma_epilogue), conv_hdmap_k / conv_c64p_k (EPI 2)
-    return wmajor && !a.resid && lbc_conv3x3_halo_eligible(a, mode); // conv3x3_c64_k<1, true>
+    if (lbc_opt_on(kOptNoBnBwdFuse) || p.mode != 1 || !a.act_bf16) return false;
+    if (p.cfg >= kLbcCfgGlds) return true;          // conv_glds2_k (lds_dma_epilogue), conv_hdmap_k / conv_c64p_k (EPI 2)
+    return p.wmajor && !a.resid && lbc_conv3x3_halo_eligible(a, p.mode); // conv3x3_c64_k<1, true>
 }
 
-bool lbc_igemm_fuses_bn_bwd_masked(const IgemmArgs& a, int wmajor, int mode, int cfg)
+bool lbc_igemm_fuses_bn_bwd_masked(const IgemmArgs& a, const IgemmPlan& p)
 {
-    (void)wmajor;
-    if (lbc_opt(kOptNoBnBwdFuse) >= 1 || mode != 1 || !a.act_bf16 || !a.resid) return false;     // (LBC_NO_BN_BWD_FUSE=2: only this form off)
-    return cfg > kLbcCfgHdma && cfg != kLbcCfgHdma + 3;      // conv_hdmap_k<.., EPI 4> (every shape) and its split-K epilogue; not the 64-channel kernel
+    if (lbc_opt(kOptNoBnBwdFuse) >= 1 || p.mode != 1 || !a.act_bf16 || !a.resid) return false;     // (LBC_NO_BN_BWD_FUSE=2: only this form off)
+    return p.cfg > kLbcCfgHdma && p.cfg != kLbcCfgHdma + 3;      // conv_hdmap_k<.., EPI 4> (every shape) and its split-K epilogue; not the 64-channel kernel
 }
 
-int lbc_igemm_pick_for(const IgemmArgs& a, int mode)
+// tile configuration for a fully described launch: the halo-staged LDS-DMA kernels' (kLbcCfgHdma + 1..4) or conv_glds.hip's
+// (kLbcCfgGlds + 0..6) when eligible, else lbc_igemm_pick
+static int lbc_igemm_pick_for(const IgemmArgs& a, int mode)
 {
     if (lbc_opt(kOptForceCfg) < 0) {     // a forced tile policy pins conv_igemm.hip
         // 3x3 stride-1 launches: the halo-staged LDS-DMA kernels first (the 64-channel layer has its own persistent variant)
@@ -586,9 +589,23 @@ int lbc_igemm_pick(long long M, int K)
     return 2;
 }
 
-int lbc_igemm_launch(const IgemmArgs& a, int wmajor, int mode, int cfg, hipStream_t s)
+// The single home of the pick rule: depth-contiguous weights (wmajor) may take an LDS-DMA family, everything else conv_igemm.hip's
+// tile policy from the GEMM extents.  Invariant: every LDS-DMA picker (lbc_conv_hdma_pick, lbc_conv_glds_pick, lbc_conv_hdmap_phased)
+// answers "not mine" unless w_bf16 && act_bf16, and bf16 weight copies exist in the depth-contiguous layout only -- so cfg >= kLbcCfgGlds
+// implies wmajor && w_bf16 && act_bf16, and lbc_igemm_pick_for falls through to lbc_igemm_pick for every other launch.
+IgemmPlan lbc_igemm_plan(const IgemmArgs& a, int wmajor, int mode)
 {
+    IgemmPlan p = {wmajor, mode, wmajor ? lbc_igemm_pick_for(a, mode) : lbc_igemm_pick(a.M, a.K), 0};
+    assert(p.cfg < kLbcCfgGlds || (wmajor && a.w_bf16 && a.act_bf16));       // (lbc_igemm_launch refuses such a plan too)
+    p.rows = lbc_igemm_rows(a, p.cfg);
+    return p;
+}
+
+int lbc_igemm_launch(const IgemmArgs& a, const IgemmPlan& p, hipStream_t s)
+{
+    const int wmajor = p.wmajor, mode = p.mode, cfg = p.cfg;
     LBC_REQUIRE(cfg >= 0 && cfg < kLbcCfgHdma + kLbcHdmaCfgs, "igemm: bad cfg %d", cfg);
+    LBC_REQUIRE(cfg < kLbcCfgGlds || (wmajor && a.w_bf16 && a.act_bf16), "igemm: cfg %d (an LDS-DMA kernel) needs depth-contiguous bf16 weight copies on bf16 tensors", cfg);
     LBC_REQUIRE(a.C % (a.bf16 ? 64 : 32) == 0, "igemm: gathered channels %d not a multiple of %d", a.C, a.bf16 ? 64 : 32);
     LBC_REQUIRE(!a.bf16 || wmajor, "igemm: the bf16 path needs depth-contiguous weights (transpose first)");
     LBC_REQUIRE(!a.act_bf16 || a.bf16, "igemm: bf16 activations need bf16 = 1");

@@ -175,21 +175,14 @@ Net::Net(const lbc_net_desc& d) : d_(d)
     partial2_floats_ = (size_t)64 * 2 * 640;
     partial2_ = alloc(partial2_floats_);
 
+    // the slab arena holds what the largest weight gradient asks for at max_batch (the same descriptors wgrad_launch plans from)
     size_t wg = 0;
-    auto wg_need = [&](int N, int OH, int OW, int CP, int Hq, int Wq, int CQ, int k, int s, int p) {
-        WgradArgs a;
-        memset(&a, 0, sizeof(a));
-        a.N = N; a.OH = OH; a.OW = OW; a.CP = CP; a.H = Hq; a.W = Wq; a.CQ = CQ; a.KH = k; a.KW = k; a.S = s; a.P = p;
-        a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;      // the split policy depends on the kernel that will run
-        return (size_t)lbc_wgrad_pick_split(a) * CP * k * k * CQ;
-    };
     for (const Block& b : blocks_) {
-        wg = std::max(wg, wg_need((int)NB, b.c1.OH, b.c1.OW, b.c1.Cout, b.c1.H, b.c1.W, b.c1.Cin, 3, b.c1.s, 1));
-        wg = std::max(wg, wg_need((int)NB, b.c2.OH, b.c2.OW, b.c2.Cout, b.c2.H, b.c2.W, b.c2.Cin, 3, 1, 1));
-        if (b.has_ds) wg = std::max(wg, wg_need((int)NB, b.ds.OH, b.ds.OW, b.ds.Cout, b.ds.H, b.ds.W, b.ds.Cin, 1, b.ds.s, 0));
+        wg = std::max(wg, lbc_wgrad_need(lbc_conv_wgrad_args(geom(b.c1, (int)NB))));
+        wg = std::max(wg, lbc_wgrad_need(lbc_conv_wgrad_args(geom(b.c2, (int)NB))));
+        if (b.has_ds) wg = std::max(wg, lbc_wgrad_need(lbc_conv_wgrad_args(geom(b.ds, (int)NB))));
     }
-    for (int i = 0; i < 3; ++i)
-        wg = std::max(wg, wg_need((int)NB, dec_[i].H, dec_[i].W, dec_[i].Cin, 2 * dec_[i].H, 2 * dec_[i].W, dec_[i].Cout, 3, 2, 1));
+    for (int i = 0; i < 3; ++i) wg = std::max(wg, lbc_wgrad_need(lbc_deconv_wgrad_args(geom(dec_[i], (int)NB))));
     wg = std::max(wg, (size_t)lbc_stem_wgrad_split((int)NB, H0, W0, Cin, stem_bf16_) * 64 * 49 * Cin);
     if (defer_wgrad_) {
         // a stage's 3x3 / stride-1 convolutions share one shape: the slabs of their grouped launch, and one dY slot per convolution
@@ -203,10 +196,7 @@ Net::Net(const lbc_net_desc& d) : d_(d)
                 dy += (b.has_ds ? 3 : 2) * slot;
             }
             const Conv& c = blocks_[last - 1].c2;
-            WgradArgs a;
-            memset(&a, 0, sizeof(a));
-            a.N = (int)NB; a.OH = c.OH; a.OW = c.OW; a.CP = c.Cout; a.H = c.H; a.W = c.W; a.CQ = c.Cin; a.KH = 3; a.KW = 3; a.S = 1; a.P = 1;
-            a.bf16 = 1; a.act_bf16 = 1; a.p = &a; a.q = &a;
+            const WgradArgs a = lbc_conv_wgrad_args(geom(c, (int)NB));
             if (lbc_wgrad_tr_eligible(a)) {
                 // (the members split into groups by their on-load transform: any group size up to the member count can occur)
                 for (int n = 1; n <= (int)std::min(members, (size_t)kLbcWgradGroupMax); ++n)
@@ -293,26 +283,19 @@ int Net::check_bound(bool need_grads) const
 int Net::conv_fwd(const Conv& c, const float* x, int N, bool stats, int* rows, hipStream_t s, const BN* pre, const BN* post,
                   const float* resid, bool relu, float* out, float* stats_buf, size_t stats_cap)
 {
-    IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.w = P(c.w); a.y = out ? out : W(c.y);
+    IgemmArgs a = lbc_conv_fwd_args(geom(c, N), pre != nullptr);
+    a.x = x; a.w = act_bf16_ ? W(c.wn) : P(c.w); a.y = out ? out : W(c.y);
     if (pre) { a.pre_scale = W(pre->scale); a.pre_shift = W(pre->shift); a.pre_relu = 1; }
     if (post) { a.post_scale = W(post->scale); a.post_shift = W(post->shift); }
     a.resid = resid; a.relu = relu ? 1 : 0;
-    a.N = N; a.H = c.H; a.W = c.W; a.C = c.Cin;
-    a.OH = c.OH; a.OW = c.OW; a.K = c.Cout;
-    a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
-    a.M = N * c.OH * c.OW; a.LH = c.OH; a.LW = c.OW; a.ostep = 1;
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
-    if (act_bf16_) { a.w = W(c.wn); a.w_bf16 = 1; }
     split_scratch(a);
-    const int cfg = lbc_igemm_pick_for(a, 0);
-    *rows = lbc_igemm_rows(a, cfg);
+    const IgemmPlan plan = lbc_igemm_plan(a, 1, 0);
+    *rows = plan.rows;
     a.stats = stats ? (stats_buf ? stats_buf : W(partial_)) : nullptr;
     // (the row count is the kernel's, known before the launch: a caller-provided statistics buffer is checked BEFORE anything is written)
     LBC_REQUIRE(!a.stats || (size_t)*rows * 2 * (size_t)c.Cout <= (stats_buf ? stats_cap : partial_floats_),
                 "net: %d statistics rows of %d channels exceed their buffer", *rows, c.Cout);
-    return lbc_igemm_launch(a, 1, 0, cfg, s);
+    return lbc_igemm_launch(a, plan, s);
 }
 
 // Split-K scratch of a convolution launch (IgemmArgs::split_ws): the weight gradients' slab arena.  Its other users are the weight-gradient
@@ -328,14 +311,7 @@ void Net::split_scratch(IgemmArgs& a) const
 // would a training forward of this convolution at batch N take conv_glds.hip when its input needs no transform on load?
 bool Net::conv_takes_glds(const Conv& c, int N, bool with_prologue) const
 {
-    if (!act_bf16_) return false;
-    IgemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.N = N; a.H = c.H; a.W = c.W; a.C = c.Cin; a.OH = c.OH; a.OW = c.OW; a.K = c.Cout;
-    a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p; a.M = N * c.OH * c.OW; a.LH = c.OH; a.LW = c.OW; a.ostep = 1;
-    a.bf16 = 1; a.act_bf16 = 1; a.w_bf16 = 1;
-    if (with_prologue) { a.pre_scale = reinterpret_cast<const float*>(this); a.pre_shift = a.pre_scale; a.pre_relu = 1; }   // (only tested for null)
-    return lbc_igemm_pick_for(a, 0) >= kLbcCfgGlds;        // conv_glds.hip or conv_hdma.hip
+    return act_bf16_ && lbc_igemm_plan(lbc_conv_fwd_args(geom(c, N), with_prologue), 1, 0).cfg >= kLbcCfgGlds;        // conv_glds.hip or conv_hdma.hip
 }
 
 int Net::weight_prep(hipStream_t s)
@@ -394,14 +370,21 @@ int Net::set_sync_bn(lbc_allreduce_fn fn, void* ctx, int world, float* buf, int 
     return LBC_OK;
 }
 
+// More than `limit` partial rows: `target` rows of their sums, in partial2_, take their place (one thread per column walking thousands
+// of rows would be the longest kernel of the layer)
+int Net::pre_reduce(const float*& part, int& rows, int width, hipStream_t s, int limit, int target)
+{
+    if (rows <= limit) return LBC_OK;
+    LBC_TRY(lbc_partial_reduce(part, rows, width, W(partial2_), target, s));
+    part = W(partial2_); rows = target;
+    return LBC_OK;
+}
+
 int Net::sync_rows(const float*& part, int& rows, int width, int n_local, hipStream_t s, float* local_lo, float* local_hi)
 {
     if (!sync_fn_) return LBC_OK;
     LBC_REQUIRE(width + 1 <= kSyncFloats, "net: %d sums do not fit the SyncBN buffer", width);
-    if (rows > kLbcFinalizeRows) {      // (one thread per column walking thousands of rows would be the longest kernel of the layer)
-        LBC_TRY(lbc_partial_reduce(part, rows, width, W(partial2_), 64, s));
-        part = W(partial2_); rows = 64;
-    }
+    LBC_TRY(pre_reduce(part, rows, width, s));
     // element `width` = this rank's batch size: its sum over the ranks gives every finalize the global element count, so no rank
     // has to know (or verify with a collective of its own) what batch the others run
     LBC_TRY(lbc_partial_reduce(part, rows, width, sync_buf_, 1, s, local_lo, local_hi, (float)n_local));
@@ -422,10 +405,8 @@ int Net::bn_finalize(const BN& bn, int rows, long long count, int n_local, int t
     } else if (train && sync_fn_) {
         LBC_TRY(sync_rows(part, rows, 2 * bn.C, n_local, s));
         nsum = part + 2 * bn.C;
-    } else if (train && rows > kLbcFinalizeRows) {
-        LBC_TRY(lbc_partial_reduce(W(partial_), rows, 2 * bn.C, W(partial2_), 64, s));
-        part = W(partial2_);
-        rows = 64;
+    } else if (train) {
+        LBC_TRY(pre_reduce(part, rows, 2 * bn.C, s));
     }
     BnFinalizeArgs f = fin_args(bn, part, rows, count, update_running);
     f.nsum = nsum; f.n_local = n_local; f.train = train;
@@ -508,13 +489,10 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
         LBC_TRY(conv_fwd(b.c1, x, N, tr, &rows, s));
         const bool fold1 = !b.fuse_z1 && can_fold(rows, b.b1.C);
         if (!fold1) LBC_TRY(bn_finalize(b.b1, rows, pix, N, train, s));
-        BnApplyArgs ap;
         if (b.fuse_z1) {
             LBC_TRY(conv_fwd(b.c2, W(b.c1.y), N, tr, &rows, s, &b.b1));
         } else {
-            memset(&ap, 0, sizeof(ap));
-            ap.x = W(b.c1.y); ap.y = W(b.z1); ap.pixels = pix; ap.C = b.c1.Cout;
-            ap.scale = W(b.b1.scale); ap.shift = W(b.b1.shift); ap.relu = 1; ap.act_bf16 = act_bf16_;
+            BnApplyArgs ap = apply_args(b.b1, W(b.c1.y), W(b.z1), pix, true);
             if (fold1) { ap.fold = 1; ap.fin = fin_args(b.b1, W(partial_), rows, pix); }
             LBC_TRY(lbc_bn_apply(ap, s));
             LBC_TRY(conv_fwd(b.c2, W(b.z1), N, tr, &rows, s));
@@ -524,9 +502,7 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
         const bool fold2 = can_fold(rows, b.b2.C) && (!b.has_ds || (size_t)lbc_cdiv(pix, 64) * 2 * b.bd.C <= partial2_floats_);
         const int rows2 = rows;
         if (!fold2) LBC_TRY(bn_finalize(b.b2, rows, pix, N, train, s));
-        memset(&ap, 0, sizeof(ap));
-        ap.x = W(b.c2.y); ap.y = W(b.out); ap.pixels = pix; ap.C = b.c2.Cout;
-        ap.scale = W(b.b2.scale); ap.shift = W(b.b2.shift); ap.relu = 1; ap.act_bf16 = act_bf16_;
+        BnApplyArgs ap = apply_args(b.b2, W(b.c2.y), W(b.out), pix, true);
         if (fold2) { ap.fold = 1; ap.fin = fin_args(b.b2, W(partial_), rows2, pix); }
         if (b.has_ds) {
             float* dsp = fold2 ? W(partial2_) : W(partial_);
@@ -560,48 +536,37 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
     const float* din = W(hcat_);
     for (int i = 0; i < 3; ++i) {
         Deconv& D = dec_[i];
-        IgemmArgs a;
-        memset(&a, 0, sizeof(a));
+        IgemmArgs a = lbc_deconv_fwd_args(geom(D, N));     // (the four output-parity phases in one launch; statistics rows ph * per + tile)
         a.x = din; a.w = P(D.w); a.y = W(D.u); a.bias = P(D.bias); a.relu = 1;
         a.pre_scale = W(D.bn.scale); a.pre_shift = W(D.bn.shift);
-        a.N = N; a.H = D.H; a.W = D.W; a.C = D.Cin;
-        a.OH = 2 * D.H; a.OW = 2 * D.W; a.K = D.Cout;
-        a.KH = 3; a.KW = 3; a.S = 2; a.P = 1;
-        a.LH = D.H; a.LW = D.W; a.ostep = 2;
-        a.M = N * D.H * D.W;
         a.stats = tr ? W(partial_) : nullptr;
-        a.act_bf16 = act_bf16_;
         int wmajor = 0;
         if (act_bf16_) {
-            a.w = W(D.wt); a.w_bf16 = 1; a.bf16 = 1; wmajor = 1;
+            a.w = W(D.wt); wmajor = 1;
         } else if (bf16_) {
             // w[Cin][T][Cout] -> wt[Cout][T][Cin]: depth-contiguous for the bf16 tiles
             LBC_TRY(lbc_weight_transpose(P(D.w), W(wt_), D.Cin, 9, D.Cout, s));
-            a.w = W(wt_); a.bf16 = 1; a.x3 = x3_; wmajor = 1;
+            a.w = W(wt_); wmajor = 1;
         }
-        a.nphase = 4;                       // the four output-parity phases in one launch; statistics rows ph * per + tile
-        int cfg = lbc_igemm_pick(a.M, a.K);
+        IgemmPlan plan = lbc_igemm_plan(a, wmajor, 1);
         if (act_bf16_) {
             // the LDS-DMA kernel cannot apply the BatchNorm on load: where it would take the launch otherwise, one bn_apply pass
             // over the (small) decoder input -- into a gradient ping-pong buffer, idle during the forward -- buys it
             IgemmArgs b = a;
             b.pre_scale = nullptr; b.pre_shift = nullptr; b.x = W(gF_);
-            const int c2 = lbc_igemm_pick_for(b, 1);
+            const IgemmPlan bare = lbc_igemm_plan(b, wmajor, 1);
             // (the 64-channel last stage too: 244 -> 167 + 25 us at 256 images, the teacher's 152 -> 112 + 15)
-            if (c2 >= kLbcCfgGlds) {
-                BnApplyArgs ap;
-                memset(&ap, 0, sizeof(ap));
-                ap.x = din; ap.y = W(gF_); ap.pixels = (long long)N * D.H * D.W; ap.C = D.Cin;
-                ap.scale = W(D.bn.scale); ap.shift = W(D.bn.shift); ap.relu = 0; ap.act_bf16 = 1;
+            if (bare.cfg >= kLbcCfgGlds) {
+                BnApplyArgs ap = apply_args(D.bn, din, W(gF_), (long long)N * D.H * D.W, false);
                 if (tr && can_fold(pend_rows, D.Cin)) { ap.fold = 1; ap.fin = fin_args(D.bn, W(partial_), pend_rows, pend_count); pend_rows = 0; }
                 else if (tr) { LBC_TRY(bn_finalize(D.bn, pend_rows, pend_count, N, train, s)); pend_rows = 0; }
                 LBC_TRY(lbc_bn_apply(ap, s));
-                a = b; cfg = c2;
+                a = b; plan = bare;
             }
         }
         if (tr && pend_rows > 0) LBC_TRY(bn_finalize(D.bn, pend_rows, pend_count, N, train, s));
-        const int per = lbc_igemm_rows(a, cfg);
-        LBC_TRY(lbc_igemm_launch(a, wmajor, 1, cfg, s));
+        const int per = plan.rows;
+        LBC_TRY(lbc_igemm_launch(a, plan, s));
         const long long opix = (long long)N * 4 * D.H * D.W;
         if (!tr) {
             // eval: statistics come from bn_eval_prep
@@ -613,14 +578,11 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
             int prow = 4 * per;
             // ONE finalize: the head kernels read the batch statistics of branch 0's slot (every branch folds its own gamma / beta
             // into the projection); the other three branches only need their running statistics and counters moved along
-            LBC_TRY(sync_rows(part, prow, 2 * 64, N, s));     // SyncBN: one all-reduce
+            LBC_TRY(sync_rows(part, prow, 2 * 64, N, s));     // SyncBN: one all-reduce (one row afterwards)
+            LBC_TRY(pre_reduce(part, prow, 2 * 64, s));
             {
                 BnFinalizeArgs f = fin_args(head_bn_[0], part, prow, opix);
                 if (sync_fn_) { f.nsum = part + 2 * 64; f.n_local = N; }
-                else if (prow > kLbcFinalizeRows) {
-                    LBC_TRY(lbc_partial_reduce(W(partial_), prow, 2 * 64, W(partial2_), 64, s));
-                    f.partial = W(partial2_); f.rows = 64;
-                }
                 for (int b = 1; b < 4; ++b) {
                     f.more_running_mean[b - 1] = P(head_bn_[b].rm); f.more_running_var[b - 1] = P(head_bn_[b].rv);
                     f.more_num_batches_tracked[b - 1] = static_cast<long long*>(t_[head_bn_[b].nbt].ptr);
@@ -632,22 +594,39 @@ int Net::forward(int N, int train, const void* image, int image_u8, const float*
     }
 
     // image.py:82-84 + common.py:29-35,136-152
+    HeadArgs ha = head_args(N, tr);
+    ha.pred_sel = pred_sel;
+    ha.scratch = W(head_partial_);       // max_batch * 20 * 65 floats >= N * 16 * 20 * 4
+    LBC_TRY(lbc_head_fwd(ha, s));
+    return lbc_copy_f32(W(pred_all_), pred_all, 40 * N, s);
+}
+
+// the head's forward and backward launches; batch_stats (training): every branch reads branch 0's batch statistics, else its own running ones
+HeadArgs Net::head_args(int N, bool batch_stats) const
+{
     HeadArgs ha;
     memset(&ha, 0, sizeof(ha));
     ha.h = W(dec_[2].u);
     for (int b = 0; b < 4; ++b) {
-        ha.mean[b] = W(head_bn_[tr ? 0 : b].mean);
-        ha.invstd[b] = W(head_bn_[tr ? 0 : b].invstd);
+        ha.mean[b] = W(head_bn_[batch_stats ? 0 : b].mean);
+        ha.invstd[b] = W(head_bn_[batch_stats ? 0 : b].invstd);
         ha.gamma[b] = P(head_bn_[b].g); ha.beta[b] = P(head_bn_[b].b);
         ha.w[b] = P(head_w_[b]); ha.bias[b] = P(head_b_[b]);
         ha.pos_x[b] = P(head_px_[b]); ha.pos_y[b] = P(head_py_[b]);
     }
     ha.cmd = W(cmd_);
-    ha.pred_all = W(pred_all_); ha.pred_sel = pred_sel; ha.rowstat = W(rowstat_);
+    ha.pred_all = W(pred_all_); ha.rowstat = W(rowstat_);
     ha.N = N; ha.OH = HH_; ha.OW = HW_; ha.act_bf16 = act_bf16_;
-    ha.scratch = W(head_partial_);       // max_batch * 20 * 65 floats >= N * 16 * 20 * 4
-    LBC_TRY(lbc_head_fwd(ha, s));
-    return lbc_copy_f32(W(pred_all_), pred_all, 40 * N, s);
+    return ha;
+}
+
+BnApplyArgs Net::apply_args(const BN& bn, const float* x, float* y, long long pixels, bool relu) const
+{
+    BnApplyArgs ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.x = x; ap.y = y; ap.pixels = pixels; ap.C = bn.C;
+    ap.scale = W(bn.scale); ap.shift = W(bn.shift); ap.relu = relu ? 1 : 0; ap.act_bf16 = act_bf16_;
+    return ap;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -683,10 +662,7 @@ int Net::bn_backward(const BN& bn, const float* dz, const float* mask, float* g_
         g_out = const_cast<float*>(dz);
     }
     const float* part = W(partial_);
-    if (rows > kLbcFinalizeRows) {
-        LBC_TRY(lbc_partial_reduce(W(partial_), rows, 2 * bn.C, W(partial2_), 64, s));
-        part = W(partial2_); rows = 64;
-    }
+    LBC_TRY(pre_reduce(part, rows, 2 * bn.C, s));
     BnBwdFinalizeArgs f;
     memset(&f, 0, sizeof(f));
     f.partial = part; f.rows = rows; f.C = bn.C; f.count = pixels;
@@ -725,13 +701,9 @@ int Net::flush_wgrads(int N, hipStream_t s)
         if (done[i]) continue;
         const PendingWgrad& pi = pending_[i];
         const Conv& c = *pi.c;
-        WgradArgs a;
-        memset(&a, 0, sizeof(a));
+        WgradArgs a = lbc_conv_wgrad_args(geom(c, N));
         a.p = pi.dy; a.q = pi.x;
         if (pi.pre) { a.q_scale = W(pi.pre->scale); a.q_shift = W(pi.pre->shift); a.q_relu = 1; }
-        a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
-        a.N = N; a.OH = c.OH; a.OW = c.OW; a.CP = c.Cout; a.H = c.H; a.W = c.W; a.CQ = c.Cin;
-        a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
         if (!lbc_wgrad_tr_eligible(a)) {
             LBC_TRY(conv_wgrad_pre(c, pi.x, pi.pre, pi.dy, N, s));
             done[i] = 1;
@@ -751,10 +723,8 @@ int Net::flush_wgrads(int N, hipStream_t s)
             ++g.n;
             done[j] = 1;
         }
-        a.nsplit = lbc_wgrad_tr_group_split(a, g.n);
-        const size_t count = (size_t)c.Cout * 9 * c.Cin;
-        // (the slab arena was planned at max_batch; the split policy is not monotone in the batch: never more slabs than it holds)
-        if ((size_t)a.nsplit * g.n * count > wg_floats_) a.nsplit = (int)std::max<size_t>(1, wg_floats_ / (g.n * count));
+        const size_t count = lbc_wgrad_count(a);
+        a.nsplit = clamp_split(lbc_wgrad_tr_group_split(a, g.n), g.n * count);
         for (int m = 0; m < g.n; ++m) g.out[m] = a.nsplit == 1 ? grads[m] : W(wg_partial_) + (size_t)m * a.nsplit * count;
         LBC_TRY(lbc_wgrad_tr_group_launch(a, g, s));
         if (a.nsplit > 1) LBC_TRY(lbc_splitk_reduce_group(W(wg_partial_), a.nsplit, (long long)count, g.n, grads, s));
@@ -764,29 +734,27 @@ int Net::flush_wgrads(int N, hipStream_t s)
     return LBC_OK;
 }
 
-int Net::conv_wgrad(const Conv& c, const float* x, const float* dy, int N, hipStream_t s)
-{
-    return conv_wgrad_pre(c, x, nullptr, dy, N, s);
-}
-
 int Net::conv_wgrad_pre(const Conv& c, const float* x, const BN* pre, const float* dy, int N, hipStream_t s)
 {
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = dy; a.q = x; a.partial = W(wg_partial_);
+    WgradArgs a = lbc_conv_wgrad_args(geom(c, N));
+    a.p = dy; a.q = x;
     if (pre) { a.q_scale = W(pre->scale); a.q_shift = W(pre->shift); a.q_relu = 1; }
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
-    a.N = N; a.OH = c.OH; a.OW = c.OW; a.CP = c.Cout;
-    a.H = c.H; a.W = c.W; a.CQ = c.Cin;
-    a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
-    a.nsplit = lbc_wgrad_pick_split(a);
-    {   // (planned at max_batch; kernel choice and split policy depend on the batch: never more slabs than the arena holds)
-        const size_t count = (size_t)c.Cout * c.k * c.k * c.Cin;
-        if ((size_t)a.nsplit * count > wg_floats_) a.nsplit = (int)std::max<size_t>(1, wg_floats_ / count);
-    }
-    if (a.nsplit == 1) { a.partial = G(c.w); return lbc_wgrad_launch(a, s); }   // a single slab is the gradient itself
-    LBC_TRY(lbc_wgrad_launch(a, s));
-    return lbc_splitk_reduce(a.partial, a.nsplit, (long long)c.Cout * c.k * c.k * c.Cin, G(c.w), 0.f, s);
+    return wgrad_launch(a, G(c.w), s);
+}
+
+// The slab arena was planned at max_batch (lbc_wgrad_need in the constructor); kernel choice and split policy depend on the batch and
+// are not monotone in it: never more slabs than the arena holds
+int Net::clamp_split(int nsplit, size_t floats_per_split) const
+{
+    if ((size_t)nsplit * floats_per_split > wg_floats_) return (int)std::max<size_t>(1, wg_floats_ / floats_per_split);
+    return nsplit;
+}
+
+// one weight gradient through the slab arena (a single slab is the gradient itself)
+int Net::wgrad_launch(WgradArgs a, float* grad, hipStream_t s)
+{
+    a.nsplit = clamp_split(lbc_wgrad_pick_split(a), lbc_wgrad_count(a));
+    return lbc_wgrad_run(a, W(wg_partial_), grad, 0.f, s);
 }
 
 // dx[N,H,W,Cin] = dgrad(dy) (+ resid).  For the 1x1/2 downsample only the even-even phase is touched.
@@ -794,43 +762,32 @@ int Net::conv_dgrad(const Conv& c, const float* dy, const float* resid, float* d
                     const float* bnb_y, int* fused_rows, const float* bnb_mask)
 {
     if (fused_rows) *fused_rows = 0;
-    IgemmArgs a;
-    memset(&a, 0, sizeof(a));
+    // (the 1x1 / stride-2 downsample accumulates onto dx in place: only the even-even phase, the one with a tap, is launched)
+    IgemmArgs a = lbc_conv_dgrad_args(geom(c, N), /*skip_empty_phases=*/true);
     a.x = dy; a.w = P(c.w); a.y = dx; a.resid = resid;
-    a.N = N; a.H = c.OH; a.W = c.OW; a.C = c.Cout;
-    a.OH = c.H; a.OW = c.W; a.K = c.Cin;
-    a.KH = c.k; a.KW = c.k; a.S = c.s; a.P = c.p;
     int wmajor = 0;
-    a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
     if (act_bf16_) {
-        a.w = W(c.wt); a.w_bf16 = 1; wmajor = 1;
+        a.w = W(c.wt); wmajor = 1;
     } else if (dgrad_wt_ && (c.k == 3 || bf16_)) {
         // w[Cout][T][Cin] -> wt[Cin][T][Cout]: output channel (Cin) major, gathered channel (Cout) contiguous
         LBC_TRY(lbc_weight_transpose(P(c.w), W(wt_), c.Cout, c.k * c.k, c.Cin, s));
         a.w = W(wt_);
         wmajor = 1;
     }
-    if (c.s == 1) {
-        a.LH = c.H; a.LW = c.W; a.ostep = 1;
-        a.M = N * c.H * c.W;
-        split_scratch(a);
-        const int cfg = wmajor ? lbc_igemm_pick_for(a, 1) : lbc_igemm_pick(a.M, a.K);
-        if (bnb && bnb_y && fused_rows &&
-            (bnb_mask ? lbc_igemm_fuses_bn_bwd_masked(a, wmajor, 1, cfg) : lbc_igemm_fuses_bn_bwd(a, wmajor, 1, cfg))) {
-            a.bnb_y = bnb_y; a.bnb_scale = W(bnb->scale); a.bnb_shift = W(bnb->shift);
-            a.bnb_mean = W(bnb->mean); a.bnb_invstd = W(bnb->invstd);
-            a.bnb_mask = bnb_mask;
-            a.stats = W(partial_);
-            *fused_rows = lbc_igemm_rows(a, cfg);
-            LBC_REQUIRE((size_t)*fused_rows * 2 * (size_t)a.K <= partial_floats_, "net: %d rows of BatchNorm-backward sums exceed their buffer", *fused_rows);
-        }
-        return lbc_igemm_launch(a, wmajor, 1, cfg, s);
+    if (c.s == 1) split_scratch(a);
+    IgemmPlan plan = lbc_igemm_plan(a, wmajor, 1);
+    if (c.s == 1 && bnb && bnb_y && fused_rows && (bnb_mask ? lbc_igemm_fuses_bn_bwd_masked(a, plan) : lbc_igemm_fuses_bn_bwd(a, plan))) {
+        a.bnb_y = bnb_y; a.bnb_scale = W(bnb->scale); a.bnb_shift = W(bnb->shift);
+        a.bnb_mean = W(bnb->mean); a.bnb_invstd = W(bnb->invstd);
+        a.bnb_mask = bnb_mask;
+        a.stats = W(partial_);
+        // the plan of the launch as it now is: the same kernel (it said it fuses), but its rows may differ (conv_c64p.hip tiles 256 rows then)
+        const IgemmPlan fused = lbc_igemm_plan(a, wmajor, 1);
+        LBC_REQUIRE(fused.cfg == plan.cfg, "net: the fused BatchNorm-backward reduce moved an input gradient from cfg %d to %d", plan.cfg, fused.cfg);
+        plan = fused; *fused_rows = plan.rows;
+        LBC_REQUIRE((size_t)*fused_rows * 2 * (size_t)a.K <= partial_floats_, "net: %d rows of BatchNorm-backward sums exceed their buffer", *fused_rows);
     }
-    a.LH = c.H / 2; a.LW = c.W / 2; a.ostep = 2;
-    a.M = N * a.LH * a.LW;
-    a.nphase = c.k == 1 ? 1 : 4;            // 1x1: only the even-even phase; 3x3: all four parity phases in one launch
-    const int cfg = (wmajor && act_bf16_) ? lbc_igemm_pick_for(a, 1) : lbc_igemm_pick(a.M, a.K);
-    return lbc_igemm_launch(a, wmajor, 1, cfg, s);
+    return lbc_igemm_launch(a, plan, s);
 }
 
 // D: gradient wrt the block output (consumed; becomes the masked gradient); on return D points at the
@@ -899,19 +856,19 @@ int Net::block_backward(Block& b, float*& D, float*& Gbuf, float* E, float* F, h
         LBC_TRY(conv_dgrad(b.c2, E, nullptr, F, N, s, &b.b1, W(b.c1.y), &fr));        // F = dZ1 (masked when fr > 0)
         LBC_TRY(bn_backward(b.b1, F, W(b.c1.y), F, W(b.c1.y), pix, E, b.b1.C, s, &b.b1, true, fr));   // E = dY1 (mask = bn1(y1) > 0)
     } else {
-        LBC_TRY(conv_wgrad(b.c2, W(b.z1), E, N, wstream(s)));
+        LBC_TRY(conv_wgrad_pre(b.c2, W(b.z1), nullptr, E, N, wstream(s)));
         LBC_TRY(conv_dgrad(b.c2, E, nullptr, F, N, s, &b.b1, W(b.c1.y), &fr));        // F = dZ1 (masked when fr > 0)
         LBC_TRY(bn_backward(b.b1, F, W(b.z1), F, W(b.c1.y), pix, E, b.b1.C, s, nullptr, true, fr));   // E = dY1
     }
     LBC_TRY(fork(s));
-    LBC_TRY(conv_wgrad(b.c1, xin, E, N, wstream(s)));
+    LBC_TRY(conv_wgrad_pre(b.c1, xin, nullptr, E, N, wstream(s)));
     if (!b.has_ds) {
         LBC_TRY(conv_dgrad(b.c1, E, D, Gbuf, N, s));                                  // G = dgrad + identity gradient
     } else {
         LBC_TRY(conv_dgrad(b.c1, E, nullptr, Gbuf, N, s));
         LBC_TRY(bn_backward(b.bd, D, nullptr, nullptr, W(b.ds.y), pix, F, b.bd.C, s)); // F = dYd (no pending reader of F)
         LBC_TRY(fork(s));
-        LBC_TRY(conv_wgrad(b.ds, xin, F, N, wstream(s)));
+        LBC_TRY(conv_wgrad_pre(b.ds, xin, nullptr, F, N, wstream(s)));
         LBC_TRY(conv_dgrad(b.ds, F, Gbuf, Gbuf, N, s));                               // G += dgrad_1x1 (even pixels)
     }
     std::swap(D, Gbuf);
@@ -963,25 +920,13 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
         // ---- head ----
         HeadBwdArgs hb;
         memset(&hb, 0, sizeof(hb));
-        HeadArgs& ha = hb.f;
-        ha.h = W(dec_[2].u);
-        for (int b = 0; b < 4; ++b) {
-            ha.mean[b] = W(head_bn_[0].mean); ha.invstd[b] = W(head_bn_[0].invstd);
-            ha.gamma[b] = P(head_bn_[b].g); ha.beta[b] = P(head_bn_[b].b);
-            ha.w[b] = P(head_w_[b]); ha.bias[b] = P(head_b_[b]);
-            ha.pos_x[b] = P(head_px_[b]); ha.pos_y[b] = P(head_py_[b]);
-        }
-        ha.cmd = W(cmd_); ha.pred_all = W(pred_all_); ha.rowstat = W(rowstat_);
-        ha.N = N; ha.OH = HH_; ha.OW = HW_; ha.act_bf16 = act_bf16_;
+        hb.f = head_args(N, true);
         hb.d_all = d_all; hb.d_sel = d_sel; hb.s_partial = W(head_partial_); hb.dh = E; hb.chan_coef = W(head_coef_);
         LBC_TRY(lbc_head_bwd_reduce(hb, s));
         HeadBwdFinalizeArgs hf;
         memset(&hf, 0, sizeof(hf));
         hf.s_partial = W(head_partial_); hf.rows = lbc_head_bwd_rows(hb.f); hf.count = (long long)N * HH_ * HW_;
-        if (hf.rows > 8) {   // the finalize kernel is one workgroup walking the rows serially: hand it 8 pre-reduced rows
-            LBC_TRY(lbc_partial_reduce(W(head_partial_), hf.rows, 20 * 65, W(partial2_), 8, s));
-            hf.s_partial = W(partial2_); hf.rows = 8;
-        }
+        LBC_TRY(pre_reduce(hf.s_partial, hf.rows, 20 * 65, s, 8, 8));   // the finalize kernel is one workgroup walking the rows serially: hand it 8 pre-reduced rows
         for (int b = 0; b < 4; ++b) {
             hf.gamma[b] = P(head_bn_[b].g); hf.beta[b] = P(head_bn_[b].b); hf.w[b] = P(head_w_[b]);
             hf.dgamma[b] = G(head_bn_[b].g); hf.dbeta[b] = G(head_bn_[b].b);
@@ -1009,37 +954,20 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
             LBC_TRY(lbc_chan_reduce(r, 1, s));
             int rows = lbc_chan_reduce_rows(opix, D.Cout);
             const float* part = W(partial_);
-            if (rows > kLbcFinalizeRows) {
-                LBC_TRY(lbc_partial_reduce(W(partial_), rows, 2 * D.Cout, W(partial2_), 64, s));
-                part = W(partial2_); rows = 64;
-            }
+            LBC_TRY(pre_reduce(part, rows, 2 * D.Cout, s));
             BnBwdFinalizeArgs f;
             memset(&f, 0, sizeof(f));
             f.partial = part; f.rows = rows; f.C = D.Cout; f.count = opix; f.dbeta = G(D.bias);
             LBC_TRY(lbc_bn_bwd_finalize(f, s));
             // weight gradient: P = bn(x) (dense), Q = g gathered with stride 2
-            WgradArgs wa;
-            memset(&wa, 0, sizeof(wa));
-            wa.p = xin; wa.q = E; wa.partial = W(wg_partial_);
+            WgradArgs wa = lbc_deconv_wgrad_args(geom(D, N));
+            wa.p = xin; wa.q = E;
             wa.p_scale = W(D.bn.scale); wa.p_shift = W(D.bn.shift);
-            wa.N = N; wa.OH = D.H; wa.OW = D.W; wa.CP = D.Cin;
-            wa.H = 2 * D.H; wa.W = 2 * D.W; wa.CQ = D.Cout; wa.KH = 3; wa.KW = 3; wa.S = 2; wa.P = 1;
-            wa.bf16 = bf16_; wa.act_bf16 = act_bf16_; wa.x3 = x3_;
-            wa.nsplit = lbc_wgrad_pick_split(wa);
-            if ((size_t)wa.nsplit * D.Cin * 9 * D.Cout > wg_floats_) wa.nsplit = (int)std::max<size_t>(1, wg_floats_ / ((size_t)D.Cin * 9 * D.Cout));
-            if (wa.nsplit == 1) wa.partial = G(D.w);
-            LBC_TRY(lbc_wgrad_launch(wa, s));
-            if (wa.nsplit > 1) LBC_TRY(lbc_splitk_reduce(wa.partial, wa.nsplit, (long long)D.Cin * 9 * D.Cout, G(D.w), 0.f, s));
+            LBC_TRY(wgrad_launch(wa, G(D.w), s));
             // input gradient: a stride-2 gather convolution over g with the same weight tensor
-            IgemmArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = E; a.w = P(D.w); a.y = F;
-            a.N = N; a.H = 2 * D.H; a.W = 2 * D.W; a.C = D.Cout;
-            a.OH = D.H; a.OW = D.W; a.K = D.Cin; a.KH = 3; a.KW = 3; a.S = 2; a.P = 1;
-            a.M = N * D.H * D.W; a.LH = D.H; a.LW = D.W; a.ostep = 1;
-            a.bf16 = bf16_; a.act_bf16 = act_bf16_; a.x3 = x3_;
-            if (act_bf16_) { a.w = W(D.wn); a.w_bf16 = 1; }
-            LBC_TRY(lbc_igemm_launch(a, 1, 0, act_bf16_ ? lbc_igemm_pick_for(a, 0) : lbc_igemm_pick(a.M, a.K), s));   // F = d bn(x)
+            IgemmArgs a = lbc_deconv_dgrad_args(geom(D, N));
+            a.x = E; a.w = act_bf16_ ? W(D.wn) : P(D.w); a.y = F;
+            LBC_TRY(lbc_igemm_launch(a, lbc_igemm_plan(a, 1, 0), s));   // F = d bn(x)
             // BatchNorm backward; for the first decoder stage only the 512 trunk channels carry on
             float* dst = i == 0 ? bwd_D_ : E;
             LBC_TRY(bn_backward(D.bn, F, nullptr, nullptr, xin, ipix, dst, i == 0 ? 512 : D.Cin, s));
@@ -1071,10 +999,7 @@ int Net::backward_impl(const float* d_sel, const float* d_all, int stage, hipStr
         int rows = lbc_pool_bwd_rows(N, H0 / 2, W0 / 2, 64);
         const long long pix = (long long)N * (H0 / 2) * (W0 / 2);
         const float* part = W(partial_);
-        if (rows > kLbcFinalizeRows) {
-            LBC_TRY(lbc_partial_reduce(W(partial_), rows, 128, W(partial2_), 64, s));
-            part = W(partial2_); rows = 64;
-        }
+        LBC_TRY(pre_reduce(part, rows, 128, s));
         BnBwdFinalizeArgs f;
         memset(&f, 0, sizeof(f));
         f.partial = part; f.rows = rows; f.C = 64; f.count = pix;

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "conv_desc.hpp"
 #include "lbc_common.hpp"
 #include "lbc_hip.h"
 #include "lbc_kernels.hpp"
@@ -120,6 +121,15 @@ private:
         return lbc_bn_fold_ok(1, C) ? lbc_bn_fold_max_rows(C) : 0;
     }
     int bn_eval_prep(hipStream_t s);
+    // a layer at batch N as the descriptor builders (conv_desc.hpp) take it; bf16 weight copies exist exactly where the activations are bf16
+    ConvGeom geom(const Conv& c, int N) const { return ConvGeom{N, c.H, c.W, c.Cin, c.Cout, c.k, c.k, c.s, c.p, bf16_, act_bf16_, act_bf16_, x3_}; }
+    ConvGeom geom(const Deconv& D, int N) const { return ConvGeom{N, D.H, D.W, D.Cin, D.Cout, 3, 3, 2, 1, bf16_, act_bf16_, act_bf16_, x3_}; }
+    // y = relu?(bn(x)) over `pixels` pixels (callers add the residual / the folded finalize)
+    BnApplyArgs apply_args(const BN& bn, const float* x, float* y, long long pixels, bool relu) const;
+    HeadArgs head_args(int N, bool batch_stats) const;
+    int pre_reduce(const float*& part, int& rows, int width, hipStream_t s, int limit = kLbcFinalizeRows, int target = 64);
+    int clamp_split(int nsplit, size_t floats_per_split) const;
+    int wgrad_launch(WgradArgs a, float* grad, hipStream_t s);
     int conv_wgrad_pre(const Conv& c, const float* x, const BN* pre, const float* dy, int N, hipStream_t s);
     bool dgrad_wt_ = false;  // bf16 operands on f32 tensors (precision 1): input-gradient GEMMs read a per-step transposed copy of the weights
     size_t wt_ = 0;
@@ -154,9 +164,6 @@ private:
     hipStream_t side_ = nullptr;
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     bool side_allowed_ = true, side_on_ = false, side_dirty_ = false;
-    int conv_wgrad(const Conv& c, const float* x, const float* dy, int N, hipStream_t s);
-    // bnb (+ bnb_y): fuse the reduce pass of that BatchNorm's backward into the epilogue when the kernel can (*fused_rows = partial
-    // rows written to partial_, else 0)
     // bnb / bnb_y: fuse the BatchNorm-backward reduce of relu(bnb(bnb_y)) into the epilogue (mask = bnb(bnb_y) > 0); with bnb_mask the mask
     // is that tensor > 0 (the ReLU output of a block: relu(bnb(bnb_y) + identity)) and the launch may carry a residual.  *fused_rows > 0:
     // the launch did it (dx is the masked gradient, partial_ holds that many rows of sums)

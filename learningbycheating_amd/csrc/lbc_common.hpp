@@ -132,10 +132,16 @@ struct IgemmArgs {
     long long split_ws_floats;
     int x3;               // 1: split-bf16 operands, hi*hi + hi*lo + lo*hi on the bf16 MFMA (requires bf16 = 1, f32 tensors and weights)
 };
-// true when the kernel a (cfg, wmajor, mode) launch takes implements IgemmArgs::bnb_*
-bool lbc_igemm_fuses_bn_bwd(const IgemmArgs& a, int wmajor, int mode, int cfg);
+// Which kernel takes a launch: weight layout and GEMM orientation as the caller has them, the tile configuration picked for them
+// (0..2: conv_igemm.hip / conv_halo.hip; kLbcCfgGlds + i: conv_glds.hip; kLbcCfgHdma + i: conv_hdmap.hpp / conv_c64p.hip) and the
+// M tiles (= statistics rows; per phase when nphase = 4) of that kernel.  Made by lbc_igemm_plan only, for a fully described launch:
+// the pickers test resid / pre_scale / bnb_y / split_ws for NULL, so a planning query carries what the launch will carry.
+struct IgemmPlan { int wmajor, mode, cfg, rows; };
+IgemmPlan lbc_igemm_plan(const IgemmArgs& a, int wmajor, int mode);
+// true when the kernel the plan names implements IgemmArgs::bnb_*
+bool lbc_igemm_fuses_bn_bwd(const IgemmArgs& a, const IgemmPlan& p);
 // ... and IgemmArgs::bnb_mask (+ a residual): conv_hdmap_k<.., EPI 4> and the split-K epilogue
-bool lbc_igemm_fuses_bn_bwd_masked(const IgemmArgs& a, int wmajor, int mode, int cfg);
+bool lbc_igemm_fuses_bn_bwd_masked(const IgemmArgs& a, const IgemmPlan& p);
 
 // One launch converts every convolution weight of a network to bf16, in its own layout w[A][T][B] and transposed
 // wt[B][T][A] (the depth-contiguous operand of the input-gradient / transposed-convolution GEMMs).
@@ -156,10 +162,7 @@ struct WeightPrepArgs {
 };
 int lbc_weight_prep(const WeightPrepArgs& a, hipStream_t s);
 
-int lbc_igemm_rows(const IgemmArgs& a, int cfg);   // number of M tiles (= stats rows) of a launch
-int lbc_igemm_pick(long long M, int K);            // tile configuration 0..2 of conv_igemm.hip from the GEMM extents alone
-// tile configuration for a fully described launch: conv_glds.hip's (kLbcCfgGlds + 0..2) when eligible, else lbc_igemm_pick
-int lbc_igemm_pick_for(const IgemmArgs& a, int mode);
+int lbc_igemm_pick(long long M, int K);            // tile configuration 0..2 of conv_igemm.hip from the GEMM extents alone (the planner's fallback)
 constexpr int kLbcCfgGlds = 3;
 constexpr int kLbcGldsCfgs = 7;
 constexpr int kLbcCfgHdma = kLbcCfgGlds + kLbcGldsCfgs;     // conv_hdma.hip (policy): {0: retired, 1: 256x128, 2: 128x256, 3: the 64-channel kernel conv_c64p.hip (C = K = 64)}
@@ -178,7 +181,7 @@ int lbc_conv_glds_rows(const IgemmArgs& a, int cfg);
 int lbc_conv_glds_launch(const IgemmArgs& a, int mode, int cfg, hipStream_t s);
 // 256 zero bytes in device memory (per device, allocated on first use): source of the zero padding of LDS-DMA staging
 int lbc_zero_page(const void** p);
-int lbc_igemm_launch(const IgemmArgs& a, int wmajor, int mode, int cfg, hipStream_t s);
+int lbc_igemm_launch(const IgemmArgs& a, const IgemmPlan& p, hipStream_t s);
 int lbc_weight_transpose(const float* w, float* wt, int A, int T, int B, hipStream_t s);   // w[A][T][B] -> wt[B][T][A]
 // 3x3 / stride-1 / pad-1, C = K = 64 launches on bf16 tensors + bf16 weight copies take the halo-staged,
 // weight-stationary kernel (conv_halo.hip); statistics rows are per 128-pixel tile like the 128-row igemm tiles
